@@ -10,6 +10,11 @@ synthetic cached latents/text states resident in HBM; weights random (no network
 
     python bench.py [--gpus N --steps K --warmup W]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the side
+measurements, each a run of its own after the timed steps: the per-GEMM roofline (two extra eager
+steps), the VAE-encode timing and the CPU baseline.  --dump-outputs DIR writes what the last timed
+step computed (DIR/*.npy) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -153,6 +158,31 @@ def pmc_traffic(model: str):
         return path, json.load(f)
 
 
+DUMP_PARAM_SAMPLE = 4 << 20   # elements of the trained store written by --dump-outputs (16 MiB as float32)
+DUMP_PARAM_CHUNK = 4096
+
+
+def dump_outputs(path: str, tr, losses) -> None:
+    """--dump-outputs: what the last timed train_step handed back and left behind, as .npy files.
+    loss.npy: the loss it returned; losses.npy: the loss of every timed step in order; params.npy: the trained
+    parameter store after its optimizer update (the whole store, or a fixed seeded sample of it when it is larger
+    than DUMP_PARAM_SAMPLE elements, with the sampled runs' start offsets in params_offsets.npy).  float32, the
+    offsets float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ls = torch.stack(losses).float().cpu().numpy().astype(np.float32)
+    np.save(os.path.join(path, "loss.npy"), ls[-1:])
+    np.save(os.path.join(path, "losses.npy"), ls)
+    data = tr.model.train_store.data
+    if data.numel() > DUMP_PARAM_SAMPLE:   # DUMP_PARAM_CHUNK-element runs at seeded offsets, in store order
+        g = torch.Generator().manual_seed(0)
+        n = DUMP_PARAM_SAMPLE // DUMP_PARAM_CHUNK
+        offs = torch.randint(0, data.numel() - DUMP_PARAM_CHUNK, (n,), generator=g).sort().values.tolist()
+        np.save(os.path.join(path, "params_offsets.npy"), np.asarray(offs, dtype=np.float64))
+        data = torch.cat([data[o:o + DUMP_PARAM_CHUNK] for o in offs])
+    np.save(os.path.join(path, "params.npy"), data.float().cpu().numpy().astype(np.float32))
+
+
 def _die_with_parent():
     """child side of launch_ranks, before exec: SIGTERM when the launcher dies (a launcher killed by a timeout
     must not leave ranks running on the GPU)"""
@@ -212,14 +242,22 @@ def main():
     ap.add_argument("--tiny", action="store_true",
                     help="(tests of the bench's own legs, e.g. launch_ranks) the tiny SDXL-shaped test UNet instead of "
                          "the full network; never a metric line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true", help="skip the VAE-encode (latent caching) side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: the per-GEMM roofline (two extra eager "
+                         "steps), the VAE-encode timing and the CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-vae", action="store_true",
+                    help="with --full: skip the VAE-encode (latent caching) side measurement")
     ap.add_argument("--autotune", action="store_true",
                     help="time (tile, split-K) candidates per GEMM signature in warm-up instead of the measured plan "
                          "table / analytic plan")
     ap.add_argument("--dump-plans", default=None,
                     help="with --autotune: merge the tuned plans into this plan-table JSON (kernels.dump_plan_table)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_vae = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -347,18 +385,36 @@ def main():
     loss_val = loss_last.item()
     if not math.isfinite(loss_val):
         raise RuntimeError(f"non-finite loss {loss_val}")
+    if args.dump_outputs and rank == 0:   # before any further step moves the weights
+        dump_outputs(args.dump_outputs, tr, losses)
 
-    g_flops, g_ms, g_n = gemm_roofline(tr, batch, in_step=True)
-    i_flops, i_ms, _ = gemm_roofline(tr, batch, in_step=False)
+    gemm_rf = None
+    if args.full:
+        g_flops, g_ms, g_n = gemm_roofline(tr, batch, in_step=True)
+        i_flops, i_ms, _ = gemm_roofline(tr, batch, in_step=False)
+        g_achieved = g_flops / (g_ms * 1e-3) / 1e12
+        i_achieved = i_flops / (i_ms * 1e-3) / 1e12
+        pmc_path, pmc = pmc_traffic(args.model)
+        default_shape = (args.batch, args.res) == {"sdxl": (4, 1024), "sd15": (16, 512), "sdxl-lora": (4, 1024),
+                                                   "flux": (4, 768)}[args.model]
+        gemm_rf = {
+            "achieved": round(g_achieved, 1), "frac": round(g_achieved / PEAK_BF16_TFLOPS, 4),
+            "traffic": (pmc["gemm_total_gb"] if pmc and default_shape else None),
+            "traffic_unit": "GB per step, GEMM family (FETCH_SIZE x 2 + WRITE_SIZE, memory-side L2 counters: "
+                            f"Infinity-Cache hits included), from profiles/{os.path.basename(pmc_path)} "
+                            "(PMC passes of this config's bench at its default shape)",
+            "algorithmic_gb": round(gemm_roofline.algo_bytes / 1e9, 2),
+            "kernel": "bf16 MFMA GEMM / implicit-GEMM conv (gemm2_kernel<*>, gemm_kernel, splitk_reduce_kernel)",
+            "basis": f"sum(2*M*N*K) over the {g_n} GEMM/conv launches of one step / sum of their in-step "
+                     f"HIP-event durations ({g_ms:.2f} ms of GEMM kernel time per step, summed over the main "
+                     f"and the weight-gradient stream, which run concurrently)",
+            "isolated_achieved": round(i_achieved, 1), "isolated_frac": round(i_achieved / PEAK_BF16_TFLOPS, 4),
+            "isolated_basis": f"the same launches with the side stream off, each GEMM alone on the chip "
+                              f"({i_ms:.2f} ms per step)"}
     vae = None
     if not args.no_vae:   # latent caching, reported beside the step, not part of `value`
         from tools.bench_vae import run as vae_run
         vae = vae_run(args.res, args.batch, iters=5, warmup=1, device=str(dev))
-    g_achieved = g_flops / (g_ms * 1e-3) / 1e12
-    i_achieved = i_flops / (i_ms * 1e-3) / 1e12
-    pmc_path, pmc = pmc_traffic(args.model)
-    default_shape = (args.batch, args.res) == {"sdxl": (4, 1024), "sd15": (16, 512), "sdxl-lora": (4, 1024),
-                                               "flux": (4, 768)}[args.model]
 
     imgs = args.batch * world * args.steps
     value = imgs / elapsed
@@ -423,20 +479,8 @@ def main():
         "loss_exact": loss_val,
         "losses_exact": [float(v) for v in torch.stack(losses).float().cpu()],
         "lora_forwards_fused_vs_two_launch": list(K.lora_fused_counts()),
-        "roofline": {"bound": "mfma", "achieved": round(g_achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(g_achieved / PEAK_BF16_TFLOPS, 4),
-                     "traffic": (pmc["gemm_total_gb"] if pmc and default_shape else None),
-                     "traffic_unit": "GB per step, GEMM family (FETCH_SIZE x 2 + WRITE_SIZE, memory-side L2 counters: "
-                                     f"Infinity-Cache hits included), from profiles/{os.path.basename(pmc_path)} "
-                                     "(PMC passes of this config's bench at its default shape)",
-                     "algorithmic_gb": round(gemm_roofline.algo_bytes / 1e9, 2),
-                     "kernel": "bf16 MFMA GEMM / implicit-GEMM conv (gemm2_kernel<*>, gemm_kernel, splitk_reduce_kernel)",
-                     "basis": f"sum(2*M*N*K) over the {g_n} GEMM/conv launches of one step / sum of their in-step "
-                              f"HIP-event durations ({g_ms:.2f} ms of GEMM kernel time per step, summed over the main "
-                              f"and the weight-gradient stream, which run concurrently)",
-                     "isolated_achieved": round(i_achieved, 1), "isolated_frac": round(i_achieved / PEAK_BF16_TFLOPS, 4),
-                     "isolated_basis": f"the same launches with the side stream off, each GEMM alone on the chip "
-                                       f"({i_ms:.2f} ms per step)",
+        # the per-GEMM entries (achieved, frac, traffic, isolated_*) take steps of their own: --full
+        "roofline": {"bound": "mfma", "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", **(gemm_rf or {}),
                      "step_achieved": round(achieved, 1), "step_frac": round(achieved / PEAK_BF16_TFLOPS, 4),
                      "step_basis": basis + " x per-GPU images / step time"},
         "cpu_baseline": None,

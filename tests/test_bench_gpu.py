@@ -13,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--res", "256",
-                        "--batch", "1", "--no-cpu-baseline", "--no-vae"], capture_output=True, text=True, timeout=280,
-                       cwd=ROOT)
+                        "--batch", "1", "--full", "--no-cpu-baseline", "--no-vae"], capture_output=True, text=True,
+                       timeout=280, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -26,6 +26,40 @@ def test_bench_json_line():
     rf = d["roofline"]
     assert rf["achieved"] > 0 and 0 < rf["frac"] < 1 and rf["peak"] > 0 and rf["isolated_frac"] > 0
     assert d["config"]["parallelism"] == "dp1"
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and runs none of the side measurements; --dump-outputs
+    writes what the last timed step returned and left behind as float32 .npy files, and two runs with the same
+    arguments write the same arrays (same seeded inputs; the tiny step is bit-deterministic,
+    tests/test_train_step_gpu.py).  The tiny SDXL-shaped UNet: the leg under test is the bench's."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                               "1", "--res", "128", "--batch", "2", "--tiny", "--dump-outputs", str(d)],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env) for d in dirs]
+    outs = [p.communicate(timeout=170) for p in procs]
+    for p, (so, se) in zip(procs, outs):
+        assert p.returncode == 0, se[-3000:]
+    lines = [ln for ln in outs[0][0].splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, outs[0][0][-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and len(d["step_ms_each"]) == 3 and len(d["losses_exact"]) == 3 and d["ms_per_step"] > 0
+    assert d["value"] > 0 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["cpu_baseline"] is None and d["vae_encode"] is None
+    rf = d["roofline"]
+    assert "achieved" not in rf and "isolated_achieved" not in rf and rf["step_achieved"] > 0
+    a, b = ({f.name: np.load(f) for f in sorted(x.iterdir())} for x in dirs)
+    assert {"loss.npy", "losses.npy", "params.npy"} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a["losses.npy"].tolist() == d["losses_exact"] and a["loss.npy"].tolist() == d["losses_exact"][-1:]
+    assert a["params.npy"].size > 0 and a["params.npy"].std() > 0
 
 
 def test_bench_two_ranks_json_line():

@@ -7,8 +7,9 @@ presets and every LossScaler / LossWeight / TimestepDistribution override, the f
 the per-sample losses the reference's own ModelSetupDiffusionLossMixin computed with that config
 (tests/golden/make_config_decisions.py).  Here an enum-typed stand-in is rebuilt from those
 strings, and the plugin's decisions (loss_plan / timestep_plan / optimizer) driven through
-oracle.diffusion must reproduce the reference's losses.  When /root/reference is present (the
-build container) the same decisions are also taken on the reference's real TrainConfig objects.
+oracle.diffusion must reproduce the reference's losses.  The same decisions are also taken on the
+reference's whole TrainConfig objects for those presets, rebuilt with Enum members from their record
+(tests/golden/reference_trainconfigs.json, tests/golden/make_reference_trainconfigs.py).
 """
 import json
 import sys
@@ -25,7 +26,6 @@ from onetrainer_amd.util.config.plain import PlainConfig, plain
 
 GOLD = Path(__file__).parent / "golden"
 CASES = json.load(open(GOLD / "config_decisions.json"))["cases"]
-REF = Path("/root/reference")
 NAME_OF = {v: k for k, v in LOSS_FN.items()}
 
 
@@ -78,16 +78,15 @@ def test_plain_passes_strings_and_writes_through():
     assert p.dp_bucket_mb == 256 and p.dp_reduce_fp32 is False   # build-only defaults
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference checkout only in the build container")
 @pytest.mark.parametrize("preset", ["#sd 1.5.json", "#sdxl 1.0.json", "#sdxl 1.0 LoRA.json", "#flux LoRA.json"])
 def test_real_reference_trainconfig(preset):
-    """the reference's TrainConfig object itself (enum members), loaded from its preset JSON."""
-    sys.path.insert(0, str(REF))
-    from modules.util.config.TrainConfig import TrainConfig
-    from modules.util.enum.LossScaler import LossScaler
-    c = TrainConfig.default_values()
-    with open(REF / "training_presets" / preset) as f:
-        c.from_dict(json.load(f))
+    """the reference's TrainConfig object as it loads its preset JSON (every field, Enum members in the enum
+    fields), rebuilt from its record tests/golden/reference_trainconfigs.json."""
+    sys.path.insert(0, str(GOLD))
+    from reference_trainconfig import reference_trainconfig
+    c, enums = reference_trainconfig(preset)
+    LossScaler = enums["LossScaler"]
+    assert isinstance(c.model_type, Enum) and isinstance(c.optimizer.optimizer, Enum) and c.loss_scaler in LossScaler
     p = plain(c)
     assert p.model_type == c.model_type.value and p.optimizer.optimizer == "ADAMW"
     assert p.text_encoder.train in (True, False) and p.text_encoder.dropout_probability == c.text_encoder.dropout_probability

@@ -17,7 +17,6 @@ from onetrainer_amd.util.dtype_util import dtype_plan, reference_decision, resol
 
 GOLD = Path(__file__).parent / "golden"
 CASES = json.load(open(GOLD / "dtype_decisions.json"))["cases"]
-REF = Path("/root/reference")
 
 
 def stand_in(case):
@@ -160,15 +159,14 @@ def test_train_script_starts_from_the_reference_defaults(tmp_path):
     assert plan.master and [o["field"] for o in plan.overrides] == ["train_dtype", "norm gradients", "grad_scaler"]
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference checkout only in the build container")
 @pytest.mark.parametrize("preset", ["#sd 1.5.json", "#sdxl 1.0.json", "#sdxl 1.0 LoRA.json", "#flux LoRA.json"])
 def test_real_reference_trainconfig(preset):
-    """the plan taken on the reference's own enum-typed TrainConfig object equals the one taken on the record"""
-    sys.path.insert(0, str(REF))
-    from modules.util.config.TrainConfig import TrainConfig
-    c = TrainConfig.default_values()
-    with open(REF / "training_presets" / preset) as f:
-        c.from_dict(json.load(f))
+    """the plan taken on the reference's own enum-typed TrainConfig object (every field as the reference loads the
+    preset, rebuilt from tests/golden/reference_trainconfigs.json) equals the one taken on the record"""
+    sys.path.insert(0, str(GOLD))
+    from reference_trainconfig import reference_trainconfig
+    c, enums = reference_trainconfig(preset)
+    assert c.train_dtype in enums["DataType"] and c.unet.weight_dtype in enums["DataType"]
     key = {"#sd 1.5.json": "sd15", "#sdxl 1.0.json": "sdxl", "#sdxl 1.0 LoRA.json": "sdxl_lora",
            "#flux LoRA.json": "flux_lora"}[preset]
     rec = case(key)

@@ -50,7 +50,7 @@ def main():
     print(f"join column: {key}; kernels columns: {kc}; regions columns: {rc}")
     ks = c.execute(f"select name, stream_id, start, end, {key} from kernels order by start").fetchall()
     marks = [r[2] for r in ks if a.marker in r[0]]
-    t0, t1 = marks[-4], marks[-3]     # the last timed step (bench.py runs two roofline steps after it)
+    t0, t1 = marks[-4], marks[-3]     # the last timed step (bench.py --full runs two roofline steps after it)
     step = [r for r in ks if t0 < r[2] <= t1]
     launch = {}
     allocs = []

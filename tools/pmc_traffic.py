@@ -4,7 +4,7 @@ gfx950 corrections (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports half t
 (16 B/lane) coalesced read, so it is doubled; WRITE_SIZE is exact for 16 B/lane stores.  Both are
 memory-side L2 counters, so Infinity-Cache hits are included (an upper bound on HBM bytes).
 One step = the dispatches after the second-to-last fused-AdamW (bf16 or f32) launch up to and including the
-last one (bench.py's last timed step; the roofline's extra eager GEMM step comes after it and is
+last one (the last timed step of bench.py --full; the roofline's extra eager GEMM step comes after it and is
 excluded by taking the step that ends at the second-to-last AdamW when three or more exist).
 
 usage: python tools/pmc_traffic.py <fetch_dir> <write_dir>

@@ -27,7 +27,7 @@ def main() -> None:
         steps = sum(r[1] for r in rows if a.steps_kernel in r[0]) or 1
     else:
         # only whole steps between optimizer launches, skipping the first window (model init, first-shape
-        # planning, warm-up) and the last two (bench.py's two extra roofline steps run after the timed steps)
+        # planning, warm-up) and the last two (the two extra roofline steps bench.py --full runs after the timed steps)
         ev = c.execute("select name, start, end from kernels order by start").fetchall()
         marks = [s for n, s, e in ev if a.steps_kernel in n]
         lo, hi = marks[1], marks[-3]

@@ -31,7 +31,7 @@ def main():
     c = sqlite3.connect(a.db)
     rows = c.execute("select name, stream_id, queue_id, start, end from kernels order by start").fetchall()
     marks = [r[3] for r in rows if a.marker in r[0]]
-    t0, t1 = marks[-4], marks[-3]   # the last timed step (bench.py runs two roofline steps after it)
+    t0, t1 = marks[-4], marks[-3]   # the last timed step (bench.py --full runs two roofline steps after it)
     step = [r for r in rows if t0 < r[3] <= t1]
     span = (t1 - t0) / 1e6
     print(f"step span {span:.2f} ms, {len(step)} kernels")
