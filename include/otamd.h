@@ -111,19 +111,39 @@ int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long long ws_byt
 long long otamd_gemm_plan(const GemmArgs* in, int splits, int* splits_out);
 
 /* replaces: (plan override) the same GEMM with an explicit plan -- the autotuner's candidates and its
-   cached per-shape choice (kernels.py set_gemm_autotune) and the measured plan table
-   (onetrainer_amd/gemm_plans_mi355x.json).  tile: -1 v1 128x128, 0 256x256, 1 256x128, 2 128x256,
-   3 256x256/4 waves, 4 128x128/8 waves, 5 128x64, 6 64x128, 7 128x160, 8 256x160, 9 / 10 = 5 / 6 on a
-   4-deep LDS ring; splits >= 1;
+   cached per-shape choice (kernels.py set_gemm_autotune) and what otamd_gemm_resolve returns.  tile: a code of the
+   tile catalogue (csrc/gemm_tiles.h lists them; -1 is the v1 128x128 kernel); splits >= 1;
    workspace >= splits*M*N*4 bytes when splits > 1 */
 int otamd_gemm_explicit(const GemmArgs* in, int tile, int splits, void* workspace, long long ws_bytes,
                         hipStream_t stream);
 
-/* replaces: (diagnostic) the tile otamd_gemm launches for these arguments: -1 v1 128x128, 0 256x256, 1 256x128, 2 128x256, 3 256x256/4 waves,
-   4 128x128, 5 128x64, 6 64x128, 7 128x160, 8 256x160 */
+/* replaces: (diagnostic) the tile the analytic planner gives these arguments and splits (0 = automatic) */
 int otamd_gemm_plan_tile(const GemmArgs* in, int splits);
 /* workspace bytes of a `splits`-way split-K launch (fp32 slabs, + the column-sum partials when colsum is set) */
 long long otamd_gemm_ws_bytes(const GemmArgs* in, int splits);
+/* BM x BN of a tile code; OTAMD_EINVAL for a code outside the catalogue */
+int otamd_gemm_tile_dims(int tile, int* bm, int* bn);
+
+/* Plan resolution (csrc/gemm_plan.hip; host code, no GPU needed).  The measured tables are data the Python package
+   loads (gemm_plans_mi355x.json, lora_plans_mi355x.json) and stores here once per process; setting a table replaces
+   it (exclusive lock), every lookup takes a shared lock.
+   otamd_gemm_plan_key: the 16-field signature a measured plan is keyed by.
+   otamd_gemm_set_plan_table: n rows of 18 = key, tile, splits.  otamd_gemm_plan_table_size: rows loaded.
+   otamd_lora_set_plans: n rows of 6 = form, N, K, parts, M class (or -M: that exact row count), tile (-1: two launches).
+   otamd_gemm_resolve: the (tile, splits) to launch with otamd_gemm_explicit; returns its workspace bytes (< 0: invalid
+     arguments).  splits == 0: the measured plan, else the analytic one; splits > 0: the analytic tile for them.
+   otamd_lora_plan: the fused-LoRA table's tile for a site (form 0 forward / 1 input gradient, base N and K, adapter
+     parts, M rows): an exact-M entry first, then the class entry while its tile grid fills its rounds of CUs;
+     0 = no entry or refused, -1 = two launches.
+   otamd_lora_fused_tile: the tile a LoRA site launches fused on, 0 = two launches; `two_launch_base` is the base GEMM
+     of the two-launch form (second K segment attached). */
+int otamd_gemm_plan_key(const GemmArgs* in, long long key[16]);
+int otamd_gemm_set_plan_table(const long long* rows, int n);
+int otamd_gemm_plan_table_size(void);
+int otamd_lora_set_plans(const long long* rows, int n);
+long long otamd_gemm_resolve(const GemmArgs* in, int splits, int* tile, int* splits_out);
+int otamd_lora_plan(int form, int N, int K, int parts, int M);
+int otamd_lora_fused_tile(const GemmArgs* two_launch_base, int form, int parts);
 
 /* replaces: ABI check */
 int otamd_gemm_args_size(void);

@@ -88,6 +88,14 @@ SIGNATURES: dict[str, list] = {
     "otamd_gemm_explicit": [C.POINTER(GemmArgs), I, I, VP, LL, VP],
     "otamd_gemm_plan_tile": [C.POINTER(GemmArgs), I],
     "otamd_gemm_ws_bytes": [C.POINTER(GemmArgs), I],
+    "otamd_gemm_tile_dims": [I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "otamd_gemm_plan_key": [C.POINTER(GemmArgs), C.POINTER(C.c_longlong)],
+    "otamd_gemm_set_plan_table": [C.POINTER(C.c_longlong), I],
+    "otamd_gemm_plan_table_size": [],
+    "otamd_lora_set_plans": [C.POINTER(C.c_longlong), I],
+    "otamd_gemm_resolve": [C.POINTER(GemmArgs), I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "otamd_lora_plan": [I, I, I, I, I],
+    "otamd_lora_fused_tile": [C.POINTER(GemmArgs), I, I],
     "otamd_adamw_bf16": [VP, VP, VP, VP, LL, C.POINTER(AdamwGroup), I, VP, I, C.c_ulonglong, VP],
     "otamd_adamw_bf16_range": [VP, VP, VP, VP, LL, LL, C.POINTER(AdamwGroup), I, VP, I, C.c_ulonglong, VP],
     "otamd_adamw_f32": [VP, VP, VP, VP, LL, C.POINTER(AdamwGroup), I, VP, VP],
@@ -192,7 +200,7 @@ def lib():
                 continue
             fn = getattr(L, name)
             fn.argtypes = args
-            fn.restype = C.c_longlong if name.endswith(("_ws_floats", "_ws_bytes", "_slab_bytes", "_plan", "_part_floats")) else C.c_int
+            fn.restype = C.c_longlong if name.endswith(("_ws_floats", "_ws_bytes", "_slab_bytes", "_gemm_plan", "_gemm_resolve", "_part_floats")) else C.c_int
         if L.otamd_gemm_args_size() != C.sizeof(GemmArgs):   # an older build (or OTAMD_LIB_ALT revision) with another
             # GemmArgs layout would read the struct short and silently drop fields (e.g. the fused LoRA operands)
             raise RuntimeError(f"{path.name}: GemmArgs is {L.otamd_gemm_args_size()} bytes, this package's is "

@@ -19,6 +19,7 @@
 // to be bank-conflict free.  The MFMA is issued with swapped operands (B-fragment as
 // the MFMA A operand) so each lane ends with 4 consecutive output columns.
 #include "gemm.h"
+#include "gemm_tiles.h"
 
 #include <stdlib.h>
 
@@ -507,49 +508,20 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int gemm2_launch(const GemmArgs& a, int tile, int splits, hipStream_t stream);   // gemm2.hip
 
-// Plan = (tile, splits).  tile: -1 = v1 128x128 (4 waves, 2 blocks/CU), 0 = 256x256, 1 = 256x128,
-// 2 = 128x256 (8 waves, 1 block/CU, LDS-DMA).  Cost model (seconds): waves of resident tiles x
+// Plan = (tile, splits); the tile codes are gemm_tiles.h's.  Cost model (seconds): waves of resident tiles x
 // (tile MACs / relative tile throughput + fixed prologue/epilogue) + split-K slab reduce traffic.
-// Relative throughputs are from tools/gemm_bench.py on MI355X.  OTAMD_GEMM_TILE forces the tile.
+// OTAMD_GEMM_TILE forces the tile by its catalogue name.
 struct GemmPlan { int tile, splits; };
 
-static int forced_tile() {
-  static int forced = -2;
-  if (forced == -2) {
+static int forced_tile() {   // -3: not forced
+  static const int forced = [] {
     const char* e = getenv("OTAMD_GEMM_TILE");
-    forced = -3;
-    if (e) {
-      if (!strcmp(e, "v1")) forced = -1;
-      else if (!strcmp(e, "256x256")) forced = 0;
-      else if (!strcmp(e, "256x128")) forced = 1;
-      else if (!strcmp(e, "128x256")) forced = 2;
-      else if (!strcmp(e, "256x256w4")) forced = 3;
-      else if (!strcmp(e, "128x128w8")) forced = 4;
-      else if (!strcmp(e, "128x64")) forced = 5;
-      else if (!strcmp(e, "64x128")) forced = 6;
-      else if (!strcmp(e, "128x160")) forced = 7;
-      else if (!strcmp(e, "256x160")) forced = 8;
-    }
-  }
+    for (const GemmTile& t : kGemmTiles)
+      if (e && t.name && !strcmp(e, t.name)) return t.code;
+    return -3;
+  }();
   return forced;
 }
-
-// candidate tiles of the analytic plan: (tile code, BM, BN, workgroups per CU, relative per-CU
-// throughput, fixed prologue/epilogue seconds).  Tile 4 (128x128, 8 waves, 2 workgroups per CU) has
-// the smallest epilogue and fills the chip on the 4096-row SDXL level-2 shapes where 256-wide tiles
-// leave CUs idle (tools/gemm_tiles.py on MI355X: 4096x1280x1280 30.3 -> 26.2 us, 4096x10240x1280
-// 129.5 -> 114.2 us, 4096x5120x1280 69.0 -> 60.0 us).
-struct TileCand { int tile, bm, bn, per_cu; double rate, fixed; };
-// Tiles 5 (128x64) and 6 (64x128): the skinny LoRA GEMMs (t = x A^T and u = dy B with N = rank,
-// the adapter wgrads with M or N = rank), where a 128- or 256-wide tile spends 2-8x the MFMA work
-// on zero padding; three workgroups per CU (48 KiB of LDS each).
-// Tiles 7 (128x160) and 8 (256x160): N = 320 / 640 / 1280 without padding and 256 tiles for the
-// 4096 x 1280 and 16384 x 640 shapes; rates fitted to the tools/gemm_tiles.py sweep of the SDXL step.
-static const TileCand kTiles[9] = {{-1, 128, 128, 2, 0.55, 2.5e-6}, {0, 256, 256, 1, 1.0, 2.5e-6},
-                                   {1, 256, 128, 1, 0.85, 2.5e-6}, {2, 128, 256, 1, 0.85, 2.5e-6},
-                                   {4, 128, 128, 2, 0.85, 0.6e-6}, {5, 128, 64, 3, 0.55, 0.6e-6},
-                                   {6, 64, 128, 3, 0.55, 0.6e-6}, {7, 128, 160, 2, 0.9, 4e-6},
-                                   {8, 256, 160, 1, 0.9, 2.5e-6}};
 
 static bool no_tile4() {   // OTAMD_GEMM_NO_T4=1: plan without the 128x128 tile (A/B measurements)
   static const bool v = getenv("OTAMD_GEMM_NO_T4") && !strcmp(getenv("OTAMD_GEMM_NO_T4"), "1");
@@ -561,10 +533,10 @@ static GemmPlan plan_gemm(int M, int N, int K, int max_splits, bool v2_only = fa
   const int ft = forced_tile();
   GemmPlan best = {-1, 1};
   double best_t = 1e300;
-  for (const TileCand& c : kTiles) {
-    if (ft != -3 && c.tile != ft) continue;
-    if (v2_only && c.tile < 0) continue;
-    if (c.tile == 4 && ft == -3 && no_tile4()) continue;
+  for (const GemmTile& c : kGemmTiles) {
+    if (!c.candidate || (ft != -3 && c.code != ft)) continue;
+    if (v2_only && c.code < 0) continue;
+    if (c.code == 4 && ft == -3 && no_tile4()) continue;
     int prev_se = 0;
     for (int s = 1; s <= max_splits; ++s) {   // every split count (3 and 5 often fill the chip best)
       const long long kps = ((long long)(K + s - 1) / s + 63) / 64 * 64;
@@ -574,14 +546,14 @@ static GemmPlan plan_gemm(int M, int N, int K, int max_splits, bool v2_only = fa
       prev_se = se;
       // split plans are re-tiled by resolve_tile (otamd_gemm is always called with the planned
       // splits), which keeps the 256-wide tiles: the 128x128 tile is an unsplit-only candidate
-      if (se > 1 && c.tile == 4) continue;
+      if (se > 1 && c.code == 4) continue;
       const long long tiles = (long long)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn) * se;
       const long long slots = 256LL * c.per_cu;
       const long long waves = (tiles + slots - 1) / slots;
       const double tile_t = 2.0 * c.bm * c.bn * (double)kps / (cu_flops * c.rate / c.per_cu);
       double tt = waves * (tile_t + c.fixed);
       if (se > 1) tt += ((double)se * M * N * 4.0 + (double)M * N * 2.0) / 4.5e12 + 3e-6;
-      if (tt < best_t * 0.98) { best_t = tt; best = {c.tile, se}; }
+      if (tt < best_t * 0.98) { best_t = tt; best = {c.code, se}; }
     }
   }
   return best;
@@ -610,9 +582,7 @@ OTAMD_API long long otamd_gemm_plan(const GemmArgs* in, int splits, int* splits_
 
 static int resolve_tile(const GemmArgs& a, int splits, GemmPlan plan, bool v2_only);
 
-// the tile otamd_gemm would launch for these arguments and splits (0 = automatic): -1 = v1 128x128,
-// 0 = 256x256, 1 = 256x128, 2 = 128x256 (8 waves), 3 = 256x256 (4 waves), 4 = 128x128 (8 waves),
-// 5 = 128x64, 6 = 64x128, 7 = 128x160, 8 = 256x160
+// the tile otamd_gemm would launch for these arguments and splits (0 = automatic)
 OTAMD_API int otamd_gemm_plan_tile(const GemmArgs* in, int splits) {
   if (!in || in->M <= 0 || in->N <= 0 || in->K <= 0) return -9;
   const bool v2_only = in->bmode == OPM_CONV_WT || in->A2 != nullptr || in->D != nullptr;
@@ -628,11 +598,11 @@ static int resolve_tile(const GemmArgs& a, int splits, GemmPlan plan, bool v2_on
   if (splits > 1 && forced_tile() == -3) {
     tile = -1;
     double bt = 1e300;
-    for (const TileCand& c : kTiles) {
-      if ((v2_only && c.tile < 0) || c.tile == 4) continue;
+    for (const GemmTile& c : kGemmTiles) {
+      if (!c.candidate || (v2_only && c.code < 0) || c.code == 4) continue;
       const long long tiles = (long long)((a.M + c.bm - 1) / c.bm) * ((a.N + c.bn - 1) / c.bn) * splits;
       const double cost = (double)((tiles + 256LL * c.per_cu - 1) / (256LL * c.per_cu)) * c.bm * c.bn / c.rate * c.per_cu;
-      if (cost < bt * 0.98) { bt = cost; tile = c.tile; }
+      if (cost < bt * 0.98) { bt = cost; tile = c.code; }
     }
   } else if (forced_tile() != -3) {
     tile = forced_tile();
@@ -641,7 +611,7 @@ static int resolve_tile(const GemmArgs& a, int splits, GemmPlan plan, bool v2_on
   return tile;
 }
 
-// force_tile: -9 = planned; otherwise the tile code (-1 v1, 0..3 v2) and splits >= 1 as given
+// force_tile: -9 = planned; otherwise the tile code and splits >= 1 as given
 static int gemm_impl(const GemmArgs* in, int splits, int force_tile, void* workspace, long long ws_bytes,
                      hipStream_t stream) {
   if (!in) return OTAMD_EINVAL;
@@ -740,13 +710,11 @@ OTAMD_API int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long l
   return gemm_impl(in, splits, -9, workspace, ws_bytes, stream);
 }
 
-// explicit plan (the autotuner's candidates and its cached choice): tile -1 = v1 128x128, 0 = 256x256,
-// 1 = 256x128, 2 = 128x256, 3 = 256x256 (4 waves), 4 = 128x128 (8 waves, 2 workgroups per CU),
-// 5 = 128x64, 6 = 64x128 (3 workgroups per CU), 7 = 128x160, 8 = 256x160, 9 / 10 = 5 / 6 on a 4-deep LDS ring;
+// explicit plan (the autotuner's candidates and its cached choice, the measured plan table): any catalogue tile;
 // splits >= 1 (rounded to whole 64-deep K steps)
 OTAMD_API int otamd_gemm_explicit(const GemmArgs* in, int tile, int splits, void* workspace, long long ws_bytes,
                                   hipStream_t stream) {
-  if (tile < -1 || tile > 10 || splits < 1) return OTAMD_EINVAL;
+  if (!gemm_tile(tile) || splits < 1) return OTAMD_EINVAL;
   return gemm_impl(in, splits, tile, workspace, ws_bytes, stream);
 }
 

@@ -1,6 +1,7 @@
 // bf16 MFMA GEMM engine v2: launcher (the kernel template is gemm2_kernel.h, its instances are in
 // gemm2_tiles_*.hip, one translation unit per tile family so they compile in parallel).
 #include "gemm2_kernel.h"
+#include "gemm_tiles.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -27,7 +28,6 @@ int gemm2_launch(const GemmArgs& a, int tile, int splits, hipStream_t stream) {
   const long long bb = operand_bytes(a.bmode, a.B, a.ldb, a.N, a.K, a.gb);
   if (ab <= 0 || bb <= 0 || ab >= 0x7fff0000LL || bb >= 0x7fff0000LL) return OTAMD_EUNSUPPORTED;
   gemm2_fn fn = nullptr;
-  int BMv = 256, BNv = 256, NWv = 8, NSv = 2;
   const bool seg2 = a.A2 != nullptr;
   const bool cs = a.colsum != nullptr;
   if (cs && (a.amode != OPM_MN || seg2 || a.batch > 1 || (splits > 1 && !a.colsum_slab))) return OTAMD_EUNSUPPORTED;
@@ -54,15 +54,12 @@ int gemm2_launch(const GemmArgs& a, int tile, int splits, hipStream_t stream) {
     case 7: case 8: fn = gemm2_pick_d(tile, a.amode, a.bmode, seg2, cs); break;
     default: break;
   }
-  // tile geometry: (BM, BN, waves, ring depth)
-  static const int geo[11][4] = {{256, 256, 8, 2}, {256, 128, 8, 2}, {128, 256, 8, 2}, {256, 256, 4, 2}, {128, 128, 8, 2},
-                                 {128, 64, 8, 2},  {64, 128, 8, 2},  {128, 160, 8, 2}, {256, 160, 8, 2}, {128, 64, 8, 4},
-                                 {64, 128, 8, 4}};
-  if (tile >= 0 && tile < 11) { BMv = geo[tile][0]; BNv = geo[tile][1]; NWv = geo[tile][2]; NSv = geo[tile][3]; }
-  if (!fn) return OTAMD_EUNSUPPORTED;
-  if (a.D && (a.lora_pw % BNv || a.N % a.lora_pw)) return OTAMD_EUNSUPPORTED;
-  const int tiles = ((a.M + BMv - 1) / BMv) * ((a.N + BNv - 1) / BNv);
-  const int lds = NSv * (BMv + BNv + (a.D ? a.lora_r : 0)) * 128 + (cs && BMv == 256 ? (NWv * 64 / (BMv / 8)) * BMv * 4 : 0);
+  const GemmTile* g = gemm_tile(tile);
+  if (!fn || !g) return OTAMD_EUNSUPPORTED;
+  if (a.D && (a.lora_pw % g->bn || a.N % a.lora_pw)) return OTAMD_EUNSUPPORTED;
+  const int tiles = ((a.M + g->bm - 1) / g->bm) * ((a.N + g->bn - 1) / g->bn);
+  const int lds = g->ring * (g->bm + g->bn + (a.D ? a.lora_r : 0)) * 128 +
+                  (cs && g->bm == 256 ? (g->waves * 64 / (g->bm / 8)) * g->bm * 4 : 0);
   {   // the LDS opt-in once per kernel instance (a per-launch driver call costs host time on every GEMM)
     static std::mutex mu;
     static std::unordered_set<const void*> done;
@@ -70,7 +67,7 @@ int gemm2_launch(const GemmArgs& a, int tile, int splits, hipStream_t stream) {
     if (done.insert((const void*)fn).second)
       hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  hipLaunchKernelGGL(fn, dim3(tiles, a.batch > 1 ? a.batch : 1, splits), dim3(NWv * 64), lds, stream, a, (unsigned)ab,
+  hipLaunchKernelGGL(fn, dim3(tiles, a.batch > 1 ? a.batch : 1, splits), dim3(g->waves * 64), lds, stream, a, (unsigned)ab,
                      (unsigned)bb, a2b, b2b);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;

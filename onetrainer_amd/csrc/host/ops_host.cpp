@@ -5,20 +5,17 @@
 // violated contract, RuntimeError on a launcher status), and is what kernels.py dispatches to: the
 // ctypes path builds a GemmArgs struct field by field, keys the measured plan table with a 16-field
 // tuple and allocates through torch.empty -- ~10 us of Python per GEMM, ~1,700 GEMMs per SDXL step.
-// Here the shape checks read tensor metadata directly, outputs come from at::empty, the plan table is an
-// unordered_map, and split-K workspaces are cached per (device, stream) like kernels.workspace.
+// Here the shape checks read tensor metadata directly, outputs come from at::empty, the plan comes from the library
+// (otamd_gemm_resolve), and split-K workspaces are cached per (device, stream) like kernels.workspace.
 //
 // The reference has no counterpart (it launches every op through diffusers / torch from Python); the ops
 // each launcher replaces are cited in include/otamd.h.
 #include <torch/extension.h>
 
-#include <array>
-#include <map>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <shared_mutex>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -63,8 +60,8 @@ struct WsHash {
   size_t operator()(const WsKey& k) const { return std::hash<int64_t>()(k.stream) * 31 + k.dev; }
 };
 // Launchers are thread-compatible (the reference runs the VAE and text encoders in data-loader worker threads,
-// DataLoaderMgdsMixin.py:47): the only mutable state is these two caches, each behind its own mutex.  A
-// workspace is reused in the order of its own stream, so threads driving different streams never share one.
+// DataLoaderMgdsMixin.py:47): the only mutable state here is this cache behind its mutex (the plan tables live in
+// the library, behind a shared lock).  A workspace is reused in the order of its own stream, so threads driving different streams never share one.
 std::mutex g_ws_mu;
 std::unordered_map<WsKey, Tensor, WsHash> g_ws;
 
@@ -81,49 +78,12 @@ void* workspace(int64_t nbytes, const at::Device& dev, int64_t stream) {
   return it->second.data_ptr();
 }
 
-// ---- measured plan table (kernels._plan_table): 16-field signature -> (tile, splits) ----
-using PlanKey = std::array<int64_t, 16>;
-struct PlanHash {
-  size_t operator()(const PlanKey& k) const {
-    size_t h = 1469598103934665603ULL;
-    for (int64_t v : k) h = (h ^ (size_t)v) * 1099511628211ULL;
-    return h;
-  }
-};
-std::shared_mutex g_plans_mu;   // read per GEMM, written only when a table is loaded
-std::unordered_map<PlanKey, std::pair<int, int>, PlanHash> g_plans;
-
-bool lookup_plan(const PlanKey& k, int& tile, int& splits) {
-  std::shared_lock<std::shared_mutex> lk(g_plans_mu);
-  auto it = g_plans.find(k);
-  if (it == g_plans.end()) return false;
-  tile = it->second.first;
-  splits = it->second.second;
-  return true;
-}
-
-PlanKey tune_key(const GemmArgs& a) {
-  return {a.amode, a.bmode, a.M, a.N, a.K, a.A2 ? a.K1 : 0, a.batch, a.c_f32, a.bias != nullptr, a.rowvec != nullptr,
-          a.residual != nullptr, a.accumulate, a.ga.KH, a.ga.stride, a.ga.upsample, a.gb.KH};
-}
-
-int64_t ws_bytes(const GemmArgs& a, int s) {
-  if (s <= 1) return 0;
-  return (int64_t)s * a.M * a.N * 4 + (a.colsum ? (int64_t)s * a.M * 4 : 0);
-}
-
-// kernels._gemm with splits == 0 (plan table, else the library's analytic plan) or an explicit split count
+// kernels._gemm: splits == 0 is the measured plan, else the library's analytic one; or an explicit split count
 void gemm(GemmArgs& a, int splits, const at::Device& dev, int64_t stream) {
   int t = 0, s = 0;
-  if (splits == 0 && lookup_plan(tune_key(a), t, s)) {
-    const int64_t wb = ws_bytes(a, s);
-    check(otamd_gemm_explicit(&a, t, s, workspace(wb, dev, stream), wb, S(stream)), "otamd_gemm_explicit");
-    return;
-  }
-  int s_out = 0;
-  const long long wb = otamd_gemm_plan(&a, splits, &s_out);
+  const long long wb = otamd_gemm_resolve(&a, splits, &t, &s);
   req(wb >= 0, "gemm plan");
-  check(otamd_gemm(&a, s_out, wb > 0 ? workspace(wb, dev, stream) : nullptr, wb, S(stream)), "otamd_gemm");
+  check(otamd_gemm_explicit(&a, t, s, workspace(wb, dev, stream), wb, S(stream)), "otamd_gemm_explicit");
 }
 
 GemmArgs new_args() {
@@ -228,57 +188,14 @@ bool lora_fuse_conv() {
   return v;
 }
 
-// measured fused-LoRA choices (kernels._lora_plans, lora_plans_mi355x.json): (form, N, K, parts, M class) -> tile,
-// or -1 for the two launches; shapes without an entry follow the two-launch form's plan
-std::shared_mutex g_lora_plans_mu;
-std::map<std::array<int64_t, 5>, int> g_lora_plans;
-void set_lora_plans(const std::vector<std::vector<int64_t>>& rows) {
-  std::unique_lock<std::shared_mutex> lk(g_lora_plans_mu);
-  g_lora_plans.clear();
-  for (const auto& r : rows) {
-    req(r.size() == 6, "lora plan row: form, N, K, parts, mclass, tile");
-    g_lora_plans[{r[0], r[1], r[2], r[3], r[4]}] = (int)r[5];
-  }
-}
-// The entries were measured at M = 4096 / 16384 (one tile per CU or whole waves of them); at the aspect buckets' other
-// row counts a tile grid just past a multiple of the 256 CUs runs a second round for a few tiles (4160 rows on
-// 128x160 tiles: 264 tiles, ~2x the time), so an entry applies only while the grid fills its rounds >= 85 %.
-// An entry for the exact row count (class slot = -M: the aspect buckets' rows, measured) comes first, unchecked.
-int lora_plan(int64_t form, int64_t N, int64_t K, int64_t parts, int64_t M) {
-  int tile = 0;
-  {
-    std::shared_lock<std::shared_mutex> lk(g_lora_plans_mu);
-    auto ex = g_lora_plans.find({form, N, K, parts, -M});
-    if (ex != g_lora_plans.end()) return ex->second;
-    auto it = g_lora_plans.find({form, N, K, parts, M >= 8192 ? 1 : 0});
-    if (it == g_lora_plans.end()) return 0;
-    tile = it->second;
-  }
-  if (tile <= 0) return tile;
-  const int64_t bm = (tile == 1 || tile == 8) ? 256 : 128, bn = (tile == 7 || tile == 8) ? 160 : 128;
-  const int64_t tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const int64_t rounds = (tiles + 255) / 256;
-  return tiles * 100 >= rounds * 256 * 85 ? tile : 0;
-}
-
 bool lora_down_fused(GemmArgs& a, const Tensor& down2d, const Tensor& up2, const Tensor& t2d, int64_t k1, int64_t r,
                      int64_t pw, int64_t stream) {
   if (!lora_fuse_on() || r != 32 || pw <= 0 || a.N % pw || k1 % 64) return false;
   if (a.amode == OPM_CONV_FWD && !lora_fuse_conv()) return false;
   GemmArgs k = a;   // the two-launch form's base GEMM signature (plan table key)
   if (!seg2(k, t2d, up2, k1, false)) return false;
-  int tile = 0, splits = 0;
-  const int lp = a.amode == OPM_K ? lora_plan(0, a.N, k1, a.N / pw, a.M) : 0;
-  if (lp == -1) return false;
-  if (lp > 0) {
-    tile = lp;
-    splits = 1;
-  } else if (!lookup_plan(tune_key(k), tile, splits)) {
-    tile = otamd_gemm_plan_tile(&k, 0);
-    if (otamd_gemm_plan(&k, 0, &splits) < 0) return false;
-  }
-  if (splits != 1) return false;
-  if (tile == 0) tile = 4;   // no fused 256x256 instance (register cap): the 128x128 tile
+  const int tile = otamd_lora_fused_tile(&k, 0, (int)(a.N / pw));
+  if (tile == 0) return false;
   req(is_bf16(down2d) && is_bf16(up2) && is_bf16(t2d) && aligned(down2d) && aligned(up2) && aligned(t2d),
       "LoRA operands bf16, aligned");
   a.D = down2d.data_ptr(); a.ldd = ld_rows(down2d);
@@ -365,17 +282,7 @@ Tensor linear_dgrad_lora(const Tensor& dy, const Tensor& w, const Tensor& up2, c
     a.M = (int)M; a.N = (int)K; a.K = (int)N;
     GemmArgs k = a;   // the two-launch form's dgrad signature (plan table key)
     req(seg2(k, u_out, down, N, true), "linear_dgrad_lora: second segment");
-    int tile = 0, splits = 0;
-    const int lp = lora_plan(1, K, N, parts, M);
-    if (lp > 0) {
-      tile = lp;
-      splits = 1;
-    } else if (lp == 0 && !lookup_plan(tune_key(k), tile, splits)) {
-      tile = otamd_gemm_plan_tile(&k, 0);
-      if (otamd_gemm_plan(&k, 0, &splits) < 0) splits = 0;
-    }
-    if (splits == 1) {
-      if (tile == 0) tile = 4;   // no fused 256x256 instance (register cap): the 128x128 tile
+    if (const int tile = otamd_lora_fused_tile(&k, 1, (int)parts)) {
       req(aligned(upT) && aligned(downT) && aligned(u_out) && is_bf16(upT) && is_bf16(downT) && is_bf16(u_out),
           "LoRA operands bf16, aligned");
       a.D = upT.data_ptr(); a.ldd = ld_rows(upT);
@@ -728,22 +635,6 @@ Tensor geglu_bwd(const Tensor& h, const Tensor& dout, int64_t stream) {
   return dh;
 }
 
-void set_plan_table(const std::vector<std::vector<int64_t>>& rows) {
-  std::unordered_map<PlanKey, std::pair<int, int>, PlanHash> table;
-  for (const auto& r : rows) {
-    req(r.size() == 18, "plan table row: 16 key fields + tile + splits");
-    PlanKey k;
-    for (int i = 0; i < 16; ++i) k[i] = r[i];
-    table[k] = {(int)r[16], (int)r[17]};
-  }
-  std::unique_lock<std::shared_mutex> lk(g_plans_mu);
-  g_plans.swap(table);
-}
-
-int64_t plan_table_size() {
-  std::shared_lock<std::shared_mutex> lk(g_plans_mu);
-  return (int64_t)g_plans.size();
-}
 void clear_workspaces() {
   std::lock_guard<std::mutex> lk(g_ws_mu);
   g_ws.clear();
@@ -759,8 +650,7 @@ PYBIND11_MODULE(_otamd_host, m) {
   m.def("conv2d", &conv2d);
   m.def("linear_lora", &linear_lora);
   m.def("linear_dgrad_lora", &linear_dgrad_lora);
-  m.def("set_lora_plans", &set_lora_plans);
-  m.def("lora_plan", &lora_plan);   // the lookup alone (tests: the same answers as kernels._lora_plan)
+  m.def("lora_plan", &otamd_lora_plan);   // the library's lookup as this module links it (tests)
   m.def("lora_dgrad_fused_counts",
         []() { return std::make_pair((long long)g_lora_dgrad_fused, (long long)g_lora_dgrad_split); });
   m.def("conv2d_lora", &conv2d_lora);
@@ -777,8 +667,6 @@ PYBIND11_MODULE(_otamd_host, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("geglu_fwd", &geglu_fwd);
   m.def("geglu_bwd", &geglu_bwd);
-  m.def("set_plan_table", &set_plan_table);
-  m.def("plan_table_size", &plan_table_size);
   m.def("clear_workspaces", &clear_workspaces);
   m.def("gemm_args_size", []() { return (int64_t)sizeof(GemmArgs); });
   m.def("attn_args_size", []() { return (int64_t)sizeof(AttnArgs); });

@@ -134,6 +134,7 @@ _gemm_forced_splits = 0   # tools/gemm_splits.py probe: forces the split count o
 # otamd_gemm_explicit.  Candidate plans all compute the same product; they differ only in the fp32
 # summation order of split-K.
 _TUNE = {"on": False, "cache": {}, "reps": int(os.environ.get("OTAMD_TUNE_REPS", "3"))}
+# candidate tile codes (the catalogue is csrc/gemm_tiles.h)
 _TILES = tuple(int(t) for t in os.environ.get("OTAMD_TUNE_TILES", "0,1,2,3,4,5,6,7,8,-1").split(","))
 _SPLITS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 16)
 
@@ -147,15 +148,21 @@ def gemm_autotune_cache() -> dict:
 
 
 def _tune_key(a: GemmArgs) -> tuple:
-    return (a.amode, a.bmode, a.M, a.N, a.K, a.K1 if a.A2 else 0, a.batch, a.c_f32, bool(a.bias), bool(a.rowvec),
-            bool(a.residual), bool(a.accumulate), a.ga.KH, a.ga.stride, a.ga.upsample, a.gb.KH)
+    """the signature plans are keyed by (otamd_gemm_plan_key): the autotuner's cache and the measured plan table"""
+    key = (C.c_longlong * 16)()
+    check(lib().otamd_gemm_plan_key(C.byref(a), key), "otamd_gemm_plan_key")
+    return tuple(key)
 
 
 def _ws_bytes(a: GemmArgs, s: int) -> int:
-    """workspace of an s-way split-K launch (otamd_gemm_ws_bytes): fp32 slabs + fused column-sum partials."""
-    if s <= 1:
-        return 0
-    return s * a.M * a.N * 4 + (s * a.M * 4 if a.colsum else 0)
+    """workspace of an s-way split-K launch: fp32 slabs + fused column-sum partials."""
+    return lib().otamd_gemm_ws_bytes(C.byref(a), s)
+
+
+def _tile_dims(tile: int) -> tuple:
+    bm, bn = C.c_int(0), C.c_int(0)
+    check(lib().otamd_gemm_tile_dims(tile, C.byref(bm), C.byref(bn)), "otamd_gemm_tile_dims")
+    return bm.value, bn.value
 
 
 def _tune(a: GemmArgs, device) -> tuple:
@@ -204,7 +211,8 @@ def _tune(a: GemmArgs, device) -> tuple:
 # (tile, split-K) per GEMM signature, timed on MI355X by the autotuner above inside the real train steps
 # of the benchmarked configurations (bench.py --autotune --dump-plans; tools/gpu_plans.sh) and committed
 # as data: deterministic plans (the same split-K summation order in every process, so resume stays
-# bit-exact), measured rather than modelled.  Signatures not in the table use the analytic plan.
+# bit-exact), measured rather than modelled.  Signatures not in the table use the analytic plan.  Loaded here,
+# stored in the library (_planner), which resolves every plan (otamd_gemm_resolve, csrc/gemm_plan.hip).
 # OTAMD_GEMM_TABLE=0 disables it (A/B against the analytic planner).
 _TABLE_PATH = (os.environ.get("OTAMD_GEMM_TABLE_PATH")   # another table for A/B measurements
                or os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_plans_mi355x.json"))
@@ -236,7 +244,7 @@ def _skinny_split(table: dict) -> None:
         am, M, N, Kd = key[0], key[2], key[3], key[4]
         if am != 0 or t not in (5, 6) or sp != 1 or N > 128:
             continue
-        bm, bn = (128, 64) if t == 5 else (64, 128)
+        bm, bn = _tile_dims(t)
         tiles = -(-M // bm) * -(-N // bn)
         nk = -(-Kd // 64)
         if tiles < 128 and nk >= 8:
@@ -246,6 +254,10 @@ def _skinny_split(table: dict) -> None:
 def plan_source() -> str:
     n = len(_plan_table())
     return f"measured plan table ({n} signatures, {os.path.basename(_TABLE_PATH)}) + analytic" if n else "analytic"
+
+
+_KEY_FIELDS = ("amode, bmode, M, N, K, K1, batch, c_f32, bias, rowvec, residual, accumulate, ga.KH, ga.stride, "
+               "ga.upsample, gb.KH")   # the table file's legend of otamd_gemm_plan_key's fields
 
 
 def dump_plan_table(path: str, merge: bool = True) -> int:
@@ -259,8 +271,7 @@ def dump_plan_table(path: str, merge: bool = True) -> int:
     for key, (t, sp) in _TUNE["cache"].items():
         rows[tuple(int(x) for x in key)] = {"key": [int(x) for x in key], "tile": int(t), "splits": int(sp)}
     out = {"device": "MI355X (gfx950)",
-           "key": "amode, bmode, M, N, K, K1, batch, c_f32, bias, rowvec, residual, accumulate, ga.KH, ga.stride, "
-                  "ga.upsample, gb.KH",
+           "key": _KEY_FIELDS,
            "plans": sorted(rows.values(), key=lambda r: r["key"])}
     with open(path, "w") as f:
         json.dump(out, f, indent=0)
@@ -279,49 +290,53 @@ def _plan_overrides() -> dict:
 
 
 _PLAN_OVERRIDES = None
+_PLANNER = None
+
+
+def _planner():
+    """the library with both measured tables stored in it (once per process, before the first plan is resolved on
+    either host path)"""
+    global _PLANNER
+    if _PLANNER is None:
+        for fn, rows in ((lib().otamd_gemm_set_plan_table, [(*k, t, sp) for k, (t, sp) in _plan_table().items()]),
+                         (lib().otamd_lora_set_plans, [(*k, t) for k, t in _lora_plans().items()])):
+            flat = [int(v) for r in rows for v in r]
+            check(fn((C.c_longlong * len(flat))(*flat), len(rows)), "plan table")
+        _PLANNER = lib()
+    return _PLANNER
 
 
 def _gemm(a: GemmArgs, splits: int, device) -> None:
-    """splits = 0: the library plans tile shape and split-K (otamd_gemm_plan), or the autotuner's
-    cached plan when set_gemm_autotune(True)."""
+    """splits = 0: the library resolves tile shape and split-K (otamd_gemm_resolve: the measured plan table, else the
+    analytic plan), or the autotuner's cached plan when set_gemm_autotune(True)."""
     global _PLAN_OVERRIDES
     if _PLAN_OVERRIDES is None:
         _PLAN_OVERRIDES = _plan_overrides()
-    if splits == 0 and _PLAN_OVERRIDES:
-        ov = _PLAN_OVERRIDES.get((a.amode, a.bmode, a.M, a.N, a.K))
-        if ov is not None:
-            t, s = ov
-            ws_bytes = _ws_bytes(a, s)
-            ws = workspace(ws_bytes, device) if ws_bytes else None
-            check(lib().otamd_gemm_explicit(C.byref(a), t, s, _p(ws), ws_bytes, stream_handle()), "otamd_gemm_explicit")
-            return
-    if splits == 0 and _gemm_forced_splits:
-        splits = _gemm_forced_splits
     plan = None
-    if splits == 0 and _TUNE["on"]:
+    if splits == 0 and _PLAN_OVERRIDES:
+        plan = _PLAN_OVERRIDES.get((a.amode, a.bmode, a.M, a.N, a.K))
+    if plan is None and splits == 0 and _gemm_forced_splits:
+        splits = _gemm_forced_splits
+    if plan is None and splits == 0 and _TUNE["on"]:
         key = _tune_key(a)
         plan = _TUNE["cache"].get(key)
         if plan is None:
             plan = _TUNE["cache"][key] = _tune(a, device)
-    elif splits == 0:
-        plan = _plan_table().get(_tune_key(a))
     if plan is not None:
         t, s = plan
         ws_bytes = _ws_bytes(a, s)
-        ws = workspace(ws_bytes, device) if ws_bytes else None
-        check(lib().otamd_gemm_explicit(C.byref(a), t, s, _p(ws), ws_bytes, stream_handle()), "otamd_gemm_explicit")
-        return
-    s_out = C.c_int(0)
-    ws_bytes = lib().otamd_gemm_plan(C.byref(a), splits, C.byref(s_out))
-    _req(ws_bytes >= 0, "gemm plan")
-    ws = workspace(ws_bytes, device) if ws_bytes > 0 else None
-    check(lib().otamd_gemm(C.byref(a), s_out.value, _p(ws), ws_bytes, stream_handle()), "otamd_gemm")
+    else:
+        tile, s_out = C.c_int(0), C.c_int(0)
+        ws_bytes = _planner().otamd_gemm_resolve(C.byref(a), splits, C.byref(tile), C.byref(s_out))
+        _req(ws_bytes >= 0, "gemm plan")
+        t, s = tile.value, s_out.value
+    ws = workspace(ws_bytes, device) if ws_bytes else None
+    check(lib().otamd_gemm_explicit(C.byref(a), t, s, _p(ws), ws_bytes, stream_handle()), "otamd_gemm_explicit")
 
 
 # ---- native host layer ----------------------------------------------------------------------
 # csrc/host/ops_host.cpp (_lib/_otamd_host.so, built by build.py next to libotamd.so): the same functions as
-# below, one C++ call per op (shape checks on tensor metadata, at::empty outputs, the plan table in an
-# unordered_map, split-K workspaces per stream).  The Python paths below stay for the autotuner / plan
+# below, one C++ call per op (shape checks on tensor metadata, at::empty outputs, split-K workspaces per stream).  The Python paths below stay for the autotuner / plan
 # overrides / forced split-K (tools) and as the A/B reference (OTAMD_HOST=0).
 _HOST = {"mod": None, "tried": False, "off": False}
 
@@ -332,12 +347,10 @@ def _host():
         path = _lib.LIB_PATH.with_name("_otamd_host.so")
         if os.environ.get("OTAMD_HOST", "1") != "0" and path.exists() and not os.environ.get("OTAMD_LIB_ALT"):
             import importlib.util
-            lib()   # libotamd.so first (RTLD_GLOBAL): the host layer links it
+            _planner()   # libotamd.so first (RTLD_GLOBAL): the host layer links it and resolves its plans there
             spec = importlib.util.spec_from_file_location("_otamd_host", str(path))
             mod = importlib.util.module_from_spec(spec)
             spec.loader.exec_module(mod)
-            mod.set_plan_table([list(k) + [t, sp] for k, (t, sp) in _plan_table().items()])
-            mod.set_lora_plans([list(k) + [t] for k, t in _lora_plans().items()])
             import atexit
             atexit.register(mod.clear_workspaces)   # free the cached workspaces while the allocator still exists
             _HOST["mod"] = mod
@@ -479,39 +492,28 @@ _LORA_PLANS: dict = {}
 
 def _lora_plans() -> dict:
     """(form, N, K, parts, M class) -> fused tile or -1 (two launches): lora_plans_mi355x.json (OTAMD_LORA_PLANS=0:
-    none, the two-launch form's plan decides -- the A/B reference)"""
-    if not _LORA_PLANS and os.environ.get("OTAMD_LORA_PLANS", "1") != "0":
+    none, the two-launch form's plan decides -- the A/B reference; 2 = fused tiles only, 3 = no exact-M rows)"""
+    mode = os.environ.get("OTAMD_LORA_PLANS", "1")
+    if not _LORA_PLANS and mode != "0":
         import json
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lora_plans_mi355x.json")
         with open(path) as f:
             for e in json.load(f)["plans"]:
-                mode = os.environ.get("OTAMD_LORA_PLANS", "1")   # A/B: 2 = fused tiles only, 3 = no exact-M rows
                 if (e["tile"] > 0 or mode != "2") and not ("M" in e and mode == "3"):
-                    # an exact row count is keyed as -M in the class slot (ops_host.cpp lora_plan)
+                    # an exact row count is keyed as -M in the class slot (otamd_lora_plan)
                     cls = -e["M"] if "M" in e else e["mclass"]
                     _LORA_PLANS[(e["form"], e["N"], e["K"], e["parts"], cls)] = e["tile"]
     return _LORA_PLANS
 
 
-def _lora_plan(form: int, N: int, K: int, parts: int, M: int):
-    """as ops_host.cpp lora_plan: an exact-row-count entry first; a class entry's tile applies only while its grid fills
-    its rounds of 256 CUs >= 85 %"""
-    exact = _lora_plans().get((form, N, K, parts, -M))
-    if exact is not None:
-        return exact
-    tile = _lora_plans().get((form, N, K, parts, int(M >= 8192)))
-    if not tile or tile < 0:
-        return tile
-    bm, bn = (256 if tile in (1, 8) else 128), (160 if tile in (7, 8) else 128)
-    tiles = -(-M // bm) * -(-N // bn)
-    rounds = -(-tiles // 256)
-    return tile if tiles * 100 >= rounds * 256 * 85 else None
+def _lora_plan(form: int, N: int, K: int, parts: int, M: int) -> int:
+    """otamd_lora_plan: the table's fused tile of a site, -1 for the two launches, 0 without an applicable entry"""
+    return _planner().otamd_lora_plan(form, N, K, parts, M)
 
 
 def _lora_down_fused(a: GemmArgs, down2d, up2, t2d, k1: int, r: int, pw: int, device, tile=None) -> bool:
-    """one launch computing t = A down^T (into t2d) and y = A B^T + t up2^T (GemmArgs.D); False when the plan of the
-    two-launch form's base GEMM is not a one-split launch on a tile with a fused instance (ops_host.cpp
-    lora_down_fused).  tile: force the tile (tests)."""
+    """one launch computing t = A down^T (into t2d) and y = A B^T + t up2^T (GemmArgs.D); False when the site runs
+    as two launches (otamd_lora_fused_tile).  tile: force the tile (tests)."""
     if not _LORA_FUSE["on"] or r != 32 or pw <= 0 or a.N % pw or k1 % 64:
         return False
     if tile is None and a.amode == OPM_CONV_FWD and not _LORA_FUSE["conv"]:   # ops_host.cpp lora_fuse_conv
@@ -519,23 +521,10 @@ def _lora_down_fused(a: GemmArgs, down2d, up2, t2d, k1: int, r: int, pw: int, de
     k = GemmArgs.from_buffer_copy(a)
     if not _seg2(k, t2d, up2, k1, False):
         return False
-    lp = _lora_plan(0, a.N, k1, a.N // pw, a.M) if tile is None and a.amode == OPM_K else None
-    if lp == -1:
-        return False
-    if lp:
-        tile = lp
     if tile is None:
-        plan = _plan_table().get(_tune_key(k))
-        if plan is None:
-            s_out = C.c_int(0)
-            if lib().otamd_gemm_plan(C.byref(k), 0, C.byref(s_out)) < 0:
-                return False
-            plan = (lib().otamd_gemm_plan_tile(C.byref(k), 0), s_out.value)
-        tile, splits = plan
-        if splits != 1:
+        tile = _planner().otamd_lora_fused_tile(C.byref(k), 0, a.N // pw)
+        if tile == 0:
             return False
-        if tile == 0:   # no fused 256x256 instance (register cap): the 128x128 tile
-            tile = 4
     _req(down2d.dtype == BF16 and up2.dtype == BF16 and t2d.dtype == BF16 and _aligned(down2d) and _aligned(up2)
          and _aligned(t2d), "LoRA operands bf16, aligned")
     a.D, a.ldd = _p(down2d), _ld_rows(down2d)
@@ -650,22 +639,9 @@ def linear_dgrad_lora(dy: torch.Tensor, w: torch.Tensor, up2: torch.Tensor, down
         a.M, a.N, a.K = M, Kd, N
         k = GemmArgs.from_buffer_copy(a)
         _req(_seg2(k, u_out, down, N, True), "linear_dgrad_lora: second segment")
-        splits = 1
-        lp = _lora_plan(1, Kd, N, parts, M) if tile is None else None
-        if lp == -1:
-            splits = 0
-        elif lp:
-            tile = lp
-        if tile is None and lp != -1:
-            plan = _plan_table().get(_tune_key(k))
-            if plan is None:
-                s_out = C.c_int(0)
-                plan = (lib().otamd_gemm_plan_tile(C.byref(k), 0),
-                        s_out.value if lib().otamd_gemm_plan(C.byref(k), 0, C.byref(s_out)) >= 0 else 0)
-            tile, splits = plan
-            if tile == 0:   # no fused 256x256 instance (register cap): the 128x128 tile
-                tile = 4
-        if splits == 1:
+        if tile is None:
+            tile = _planner().otamd_lora_fused_tile(C.byref(k), 1, parts)
+        if tile:
             _req(all(t.dtype == BF16 and _aligned(t) for t in (upT, downT, u_out)), "LoRA operands bf16, aligned")
             a.D, a.ldd = _p(upT), _ld_rows(upT)
             a.B2, a.ldb2 = _p(downT), _ld_rows(downT)
