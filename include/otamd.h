@@ -430,6 +430,23 @@ int otamd_mse_loss(const void* pred, int cpad, const void* target, int tgt_f32, 
 int otamd_mse_grad(const void* pred, int cpad, const void* target, int tgt_f32, int B, long long HW, int C,
     const float* coef, const float* grad_out, void* dpred, hipStream_t s);
 
+/* replaces: ModelSetupDiffusionLossMixin.__masked_losses / __unmasked_losses with the MSE, MAE and log-cosh terms
+   (ModelSetupDiffusionLossMixin.py:27-150) + masked_losses_with_prior with masked_prior_preservation_weight == 0
+   (modules/util/loss/masked_loss.py:21-37) + the scalers, loss_weight, timestep weight and .mean() of otamd_mse_loss.
+   mask: float [B, HW] (one value per latent pixel, clamped to [unmasked_weight, 1], broadcast over the channels) or
+   NULL (unmasked; normalize is then ignored).  A strength of exactly 0 skips its term; all three 0 is EINVAL.
+   ws: float[4 * B * ceil(HW * C / 2048)].  Out: loss[1], coef[B, 3] (mse, mae, log-cosh), losses[B] (nullable). */
+int otamd_diffusion_loss(const void* pred, int cpad, const void* target, int tgt_f32, const float* mask, int B,
+    long long HW, int C, float mse_strength, float mae_strength, float log_cosh_strength, float unmasked_weight,
+    int normalize, float scale, const float* loss_weight, const int* timestep, const float* sqrt_acp,
+    const float* sqrt_1m, int loss_fn, float gamma, int v_pred, int num_t, float ga, float* ws, long long ws_floats,
+    float* loss_out, float* coef, float* losses_out, hipStream_t s);
+
+/* replaces: autograd of the loss above: dpred = m (2 d coef[b,0] + sign(d) coef[b,1] + tanh(d) coef[b,2]) grad_out[0],
+   bf16, pad channels 0 */
+int otamd_diffusion_loss_grad(const void* pred, int cpad, const void* target, int tgt_f32, const float* mask, int B,
+    long long HW, int C, float unmasked_weight, const float* coef, const float* grad_out, void* dpred, hipStream_t s);
+
 /* replaces: AdamW step_adamw_parameter + addcdiv_stochastic_ (modules/util/optimizer/adamw_extensions.py:17-150; modules/util/bf16_stochastic_rounding.py:5-61), patched at modules/util/create.py:509-534 */
 int otamd_adamw_bf16(void* p, const void* g, void* m, void* v, long long n, const AdamwGroup* groups, int
     n_groups, const float* clip_coef, int stochastic_rounding, unsigned long long seed, hipStream_t stream);

@@ -178,6 +178,9 @@ SIGNATURES: dict[str, list] = {
     "otamd_flow_prologue": [VP, VP, I, VP, F, F, I, I, LL, I, I, VP, VP, VP],
     "otamd_mse_loss": [VP, I, VP, I, I, LL, I, F, F, VP, VP, VP, VP, I, F, I, I, F, VP, LL, VP, VP, VP, VP],
     "otamd_mse_grad": [VP, I, VP, I, I, LL, I, VP, VP, VP, VP],
+    "otamd_diffusion_loss": [VP, I, VP, I, VP, I, LL, I, F, F, F, F, I, F, VP, VP, VP, VP, I, F, I, I, F, VP, LL, VP,
+                             VP, VP, VP],
+    "otamd_diffusion_loss_grad": [VP, I, VP, I, VP, I, LL, I, F, VP, VP, VP, VP],
 }
 
 _lib = None

@@ -5,6 +5,8 @@
 //   flow-matching add-noise     modules/modelSetup/mixin/ModelSetupFlowMatchingMixin.py:14-39
 //   v-prediction target         diffusers DDIMScheduler.get_velocity (BaseStableDiffusionXLSetup.py:285)
 //   MSE loss fwd / grad         modules/modelSetup/mixin/ModelSetupDiffusionLossMixin.py:119-168,233-321
+//   masked MSE / MAE / log-cosh modules/modelSetup/mixin/ModelSetupDiffusionLossMixin.py:27-150,
+//                               modules/util/loss/masked_loss.py:21-37
 //
 // RNG: Philox4x32-10, counter = (element index of the GLOBAL batch tensor, stream id), key =
 // seed (= global_step).  Each rank draws exactly its slice of the global batch, so a DP run
@@ -201,6 +203,33 @@ __global__ void __launch_bounds__(256) mse_partial_kernel(const bf16_t* pred, in
   if (threadIdx.x == 0) partial[b * nblk + blk] = s;
 }
 
+// w times the timestep weight of sample b (ModelSetupDiffusionLossMixin.py:170-231), shared by the MSE and the
+// general finalize kernels.  loss_fn: 0 constant, 1 min-snr-gamma, 2 debiased estimation, 3 p2, 4 sigma.
+__device__ __forceinline__ float timestep_weighted(float w, int b, int loss_fn, const int* timestep,
+                                                   const float* sqrt_acp, const float* sqrt_1m, float gamma,
+                                                   int v_pred, int num_t) {
+  if (loss_fn == 4) {
+    w *= (float)(timestep[b] + 1) / (float)num_t;
+  } else if (loss_fn != 0) {
+    const int t = timestep[b];
+    const float r = sqrt_acp[t] / sqrt_1m[t];
+    float snr = r * r;
+    if (loss_fn == 1) {
+      const float mg = fminf(snr, gamma);
+      if (v_pred) snr += 1.f;
+      w *= mg / snr;
+    } else if (loss_fn == 2) {
+      snr = fminf(snr, 1000.f);
+      if (v_pred) snr += 1.f;
+      w *= rsqrtf(snr);
+    } else {
+      if (v_pred) snr += 1.f;
+      w *= powf(1.f + snr, -gamma);
+    }
+  }
+  return w;
+}
+
 // MSE pass 2 (1 block): losses[b] = mean * mse_strength * scale * loss_weight[b] * w_t[b];
 // loss = mean_b(losses) / ga ; coef[b] = d loss / d pred (without the 2*(p-t) factor)
 // loss_fn: 0 constant, 1 min-snr-gamma, 2 debiased estimation, 3 p2 (ModelSetupDiffusionLossMixin.py:170-225),
@@ -216,25 +245,7 @@ __global__ void mse_finalize_kernel(const float* partial, int nblk, int B, long 
     float s = 0.f;
     for (int k = 0; k < nblk; ++k) s += partial[b * nblk + k];
     float w = mse_strength * scale * (loss_weight ? loss_weight[b] : 1.f);
-    if (loss_fn == 4) {
-      w *= (float)(timestep[b] + 1) / (float)num_t;
-    } else if (loss_fn != 0) {
-      const int t = timestep[b];
-      const float r = sqrt_acp[t] / sqrt_1m[t];
-      float snr = r * r;
-      if (loss_fn == 1) {
-        const float mg = fminf(snr, gamma);
-        if (v_pred) snr += 1.f;
-        w *= mg / snr;
-      } else if (loss_fn == 2) {
-        snr = fminf(snr, 1000.f);
-        if (v_pred) snr += 1.f;
-        w *= rsqrtf(snr);
-      } else {
-        if (v_pred) snr += 1.f;
-        w *= powf(1.f + snr, -gamma);
-      }
-    }
+    w = timestep_weighted(w, b, loss_fn, timestep, sqrt_acp, sqrt_1m, gamma, v_pred, num_t);
     const float mean = s / (float)per;
     const float lb = mean * w;
     if (losses_out) losses_out[b] = lb;
@@ -262,6 +273,116 @@ __global__ void mse_grad_kernel(const bf16_t* pred, int cpad, const void* target
       const int b = (int)(pix / HW);
       const float d = bf2f(pred[i]) - ld_t(target, pix * C + c, tgt_f32);
       g = d * coef[b] * go;
+    }
+    dpred[i] = f2bf(g);
+  }
+}
+
+// General diffusion loss: mask-weighted MSE / MAE / log-cosh (ModelSetupDiffusionLossMixin.py:27-150 with
+// masked_losses_with_prior, modules/util/loss/masked_loss.py:21-37, masked_prior_preservation_weight == 0).
+// mask: float [B, HW], one value per latent pixel, broadcast over the channels; nullptr = unmasked (m = 1).
+__device__ __forceinline__ float mask_weight(const float* mask, long long pix, float unmasked_weight) {
+  return mask ? fminf(fmaxf(mask[pix], unmasked_weight), 1.f) : 1.f;   // torch.clamp(mask, unmasked_weight, 1)
+}
+// diff + softplus(-2 diff) - log(2), softplus with torch's threshold 20 (:27-34)
+__device__ __forceinline__ float log_cosh_term(float d) {
+  const float x = -2.0f * d;
+  const float sp = x > 20.f ? x : log1pf(expf(x));
+  return (d + sp) - 0.69314718055994531f;
+}
+
+// pass 1: per-(sample, block) partials {sum m d^2, sum m |d|, sum m lc(d), sum m}; a term whose strength is 0
+// is not evaluated (its partial is 0), so the result never depends on an unused term
+__global__ void __launch_bounds__(256) dloss_partial_kernel(const bf16_t* pred, int cpad, const void* target,
+                                                            int tgt_f32, const float* mask, float unmasked_weight,
+                                                            long long HW, int C, int use_mse, int use_mae, int use_lc,
+                                                            float* partial, int nblk) {
+  const int b = blockIdx.y, blk = blockIdx.x;
+  const long long per = HW * C;
+  const long long e0 = (long long)blk * LOSS_BLK;
+  float s2 = 0.f, s1 = 0.f, sl = 0.f, sm = 0.f;
+  for (long long e = e0 + threadIdx.x; e < min(per, e0 + LOSS_BLK); e += 256) {
+    const long long i = (long long)b * per + e;
+    const long long pix = i / C;
+    const int c = (int)(i - pix * C);
+    const float d = bf2f(pred[pix * cpad + c]) - ld_t(target, i, tgt_f32);
+    const float m = mask_weight(mask, pix, unmasked_weight);
+    if (use_mse) s2 += (d * d) * m;
+    if (use_mae) s1 += fabsf(d) * m;
+    if (use_lc) sl += log_cosh_term(d) * m;
+    sm += m;
+  }
+  __shared__ float red[4];
+  s2 = block_sum(s2, red);
+  s1 = block_sum(s1, red);
+  sl = block_sum(sl, red);
+  sm = block_sum(sm, red);
+  if (threadIdx.x == 0) {
+    float* o = partial + ((long long)b * nblk + blk) * 4;
+    o[0] = s2; o[1] = s1; o[2] = sl; o[3] = sm;
+  }
+}
+
+// pass 2 (1 block): losses[b] = (mse_s L_mse + mae_s L_mae + lc_s L_lc) * scale * loss_weight[b] * w_t[b], with
+// L = mean(term m) [/ mean(m) when normalize and masked]; loss = mean_b(losses) / ga;
+// coef[b][j] = d loss / d pred without the m * term' factor (term' = 2d, sign(d), tanh(d))
+__global__ void dloss_finalize_kernel(const float* partial, int nblk, int B, long long per, float mse_strength,
+                                      float mae_strength, float lc_strength, int normalize, float scale,
+                                      const float* loss_weight, const int* timestep, const float* sqrt_acp,
+                                      const float* sqrt_1m, int loss_fn, float gamma, int v_pred, int num_t, float ga,
+                                      float* loss_out, float* coef, float* losses_out) {
+  __shared__ float lb_s[LOSS_MAX_B];
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < nblk; ++k)
+      for (int j = 0; j < 4; ++j) s[j] += partial[((long long)b * nblk + k) * 4 + j];
+    float w = scale * (loss_weight ? loss_weight[b] : 1.f);
+    w = timestep_weighted(w, b, loss_fn, timestep, sqrt_acp, sqrt_1m, gamma, v_pred, num_t);
+    const float norm = normalize ? s[3] / (float)per : 1.f;
+    const float strength[3] = {mse_strength, mae_strength, lc_strength};
+    float base = 0.f;
+    for (int j = 0; j < 3; ++j) {
+      float cj = 0.f;
+      if (strength[j] != 0.f) {
+        float L = s[j] / (float)per;
+        if (normalize) L = L / norm;
+        base += L * strength[j];
+        cj = strength[j] * w / ((float)per * (float)B * ga * norm);
+      }
+      coef[b * 3 + j] = cj;
+    }
+    const float lb = base * w;
+    if (losses_out) losses_out[b] = lb;
+    lb_s[b] = lb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+    for (int b = 0; b < B; ++b) tot += lb_s[b];
+    loss_out[0] = tot / (float)B / ga;
+  }
+}
+
+// dpred = m (2 d coef[b][0] + sign(d) coef[b][1] + tanh(d) coef[b][2]) grad_out[0]; sign(0) = 0 (torch's L1
+// gradient); padded channels get 0; a term with coefficient 0 (strength 0) is not evaluated
+__global__ void dloss_grad_kernel(const bf16_t* pred, int cpad, const void* target, int tgt_f32, const float* mask,
+                                  float unmasked_weight, long long HW, int C, int B, const float* coef,
+                                  const float* grad_out, bf16_t* dpred) {
+  const long long total = (long long)B * HW * cpad;
+  const float go = grad_out ? grad_out[0] : 1.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % cpad);
+    const long long pix = i / cpad;
+    float g = 0.f;
+    if (c < C) {
+      const int b = (int)(pix / HW);
+      const float c2 = coef[b * 3], c1 = coef[b * 3 + 1], cl = coef[b * 3 + 2];
+      const float d = bf2f(pred[i]) - ld_t(target, pix * C + c, tgt_f32);
+      float t = 0.f;
+      if (c2 != 0.f) t += (2.f * d) * c2;
+      if (c1 != 0.f) t += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * c1;
+      if (cl != 0.f) t += tanhf(d) * cl;
+      g = mask_weight(mask, pix, unmasked_weight) * t * go;
     }
     dpred[i] = f2bf(g);
   }
@@ -358,6 +479,48 @@ OTAMD_API int otamd_mse_grad(const void* pred, int cpad, const void* target, int
   if (!pred || !target || !coef || !dpred || B <= 0 || C <= 0 || cpad < C) return OTAMD_EINVAL;
   mse_grad_kernel<<<gfor((long long)B * HW * cpad), 256, 0, s>>>((const bf16_t*)pred, cpad, target, tgt_f32, HW, C, B,
                                                                  coef, grad_out, (bf16_t*)dpred);
+  OTAMD_CHECK_LAUNCH();
+  return OTAMD_OK;
+}
+// mask: float [B, HW] or nullptr (unmasked; normalize is then ignored).  ws: float[4 * B * ceil(HW*C/2048)];
+// out: loss[1], coef[B, 3] (mse, mae, log-cosh), losses[B] (optional)
+OTAMD_API int otamd_diffusion_loss(const void* pred, int cpad, const void* target, int tgt_f32, const float* mask,
+                                   int B, long long HW, int C, float mse_strength, float mae_strength,
+                                   float log_cosh_strength, float unmasked_weight, int normalize, float scale,
+                                   const float* loss_weight, const int* timestep, const float* sqrt_acp,
+                                   const float* sqrt_1m, int loss_fn, float gamma, int v_pred, int num_t, float ga,
+                                   float* ws, long long ws_floats, float* loss_out, float* coef, float* losses_out,
+                                   hipStream_t s) {
+  if (!pred || !target || !ws || !loss_out || !coef || B <= 0 || B > LOSS_MAX_B || HW <= 0 || C <= 0 || cpad < C ||
+      loss_fn < 0 || loss_fn > 4)
+    return OTAMD_EINVAL;
+  if (!(unmasked_weight >= 0.f && unmasked_weight <= 1.f)) return OTAMD_EINVAL;
+  if (mse_strength == 0.f && mae_strength == 0.f && log_cosh_strength == 0.f) return OTAMD_EINVAL;
+  if (loss_fn == 4 && (!timestep || num_t <= 0)) return OTAMD_EINVAL;
+  if (loss_fn != 0 && loss_fn != 4 && (!timestep || !sqrt_acp || !sqrt_1m)) return OTAMD_EINVAL;
+  const long long per = HW * C;
+  const int nblk = (int)((per + LOSS_BLK - 1) / LOSS_BLK);
+  if (ws_floats < 4ll * B * nblk) return OTAMD_EINVAL;
+  dloss_partial_kernel<<<dim3(nblk, B), 256, 0, s>>>((const bf16_t*)pred, cpad, target, tgt_f32, mask, unmasked_weight,
+                                                     HW, C, mse_strength != 0.f, mae_strength != 0.f,
+                                                     log_cosh_strength != 0.f, ws, nblk);
+  OTAMD_CHECK_LAUNCH();
+  dloss_finalize_kernel<<<1, 256, 0, s>>>(ws, nblk, B, per, mse_strength, mae_strength, log_cosh_strength,
+                                          (normalize && mask) ? 1 : 0, scale, loss_weight, timestep, sqrt_acp, sqrt_1m,
+                                          loss_fn, gamma, v_pred, num_t, ga, loss_out, coef, losses_out);
+  OTAMD_CHECK_LAUNCH();
+  return OTAMD_OK;
+}
+// coef: float [B, 3] of otamd_diffusion_loss; mask / unmasked_weight as given there
+OTAMD_API int otamd_diffusion_loss_grad(const void* pred, int cpad, const void* target, int tgt_f32, const float* mask,
+                                        int B, long long HW, int C, float unmasked_weight, const float* coef,
+                                        const float* grad_out, void* dpred, hipStream_t s) {
+  if (!pred || !target || !coef || !dpred || B <= 0 || B > LOSS_MAX_B || HW <= 0 || C <= 0 || cpad < C)
+    return OTAMD_EINVAL;
+  if (!(unmasked_weight >= 0.f && unmasked_weight <= 1.f)) return OTAMD_EINVAL;
+  dloss_grad_kernel<<<gfor((long long)B * HW * cpad), 256, 0, s>>>((const bf16_t*)pred, cpad, target, tgt_f32, mask,
+                                                                   unmasked_weight, HW, C, B, coef, grad_out,
+                                                                   (bf16_t*)dpred);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

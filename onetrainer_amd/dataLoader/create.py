@@ -8,7 +8,11 @@ trainer, on this build's latent cache (dataLoader/latent_cache.py).
     prompt file ('concept') or the file name ('filename'); tokenize with the checkpoint's own
     tokenizers (<base_model>/tokenizer[_2], transformers); encode images with the HIP VAE encoder and
     text with the HIP text encoders the model carries (attach_cache_encoders, loaded by the model
-    loader with the base weights), write the cache on rank 0, then read it.
+    loader with the base weights), write the cache on rank 0, then read it;
+  * under masked_training every image is paired with <stem>-masklabel.png (DataLoaderText2ImageMixin.py:62,
+    85-86; all ones when the file is missing), cached as latent_mask and required from the cache.  The
+    per-concept mask augmentations (RandomCircularMaskShrink / RandomMaskRotateCrop, :122-135) are refused;
+    unmasked_probability only acts on mask-input (inpainting) model types (:287-288), which are not loaded.
 mgds itself is not in this image: enumeration and captions follow the reference's
 ConceptConfig fields; the bucket list is dataLoader/aspect_bucketing.py (parity unpinned).
 """
@@ -92,18 +96,36 @@ def _caption(img_path: str, concept: dict) -> str:
     return ""
 
 
-def enumerate_samples(config) -> list[tuple[str, str]]:
-    """(image path, caption) for every enabled concept (mgds CollectPaths + caption loading)."""
+MASK_POSTFIX = "-masklabel.png"
+MASK_AUGMENTATIONS = ("enable_random_circular_mask_shrink", "enable_random_mask_rotate_crop")
+
+
+def mask_path(img_path: str) -> str | None:
+    """<stem>-masklabel.png next to the image (DataLoaderText2ImageMixin.py:62), or None when there is none:
+    the sample then trains with an all-ones mask (GenerateImageLike color 255, :85)."""
+    p = os.path.splitext(img_path)[0] + MASK_POSTFIX
+    return p if os.path.isfile(p) else None
+
+
+def enumerate_samples(config) -> list[tuple]:
+    """(image path, caption) for every enabled concept (mgds CollectPaths + caption loading); under
+    masked_training (image path, caption, mask path or None).  A -masklabel.png is never listed as an image."""
     cfg = plain(config)
+    masked = bool(getattr(cfg, "masked_training", False))
     out = []
     for c in _concepts(cfg):
+        if masked:
+            on = [k for k in MASK_AUGMENTATIONS if (c.get("image") or {}).get(k)]
+            if on:
+                raise NotImplementedError(f"concept {c.get('name') or c['path']!r}: mask augmentation {on[0]} is not "
+                                          "built (masks are cached as they are)")
         root = c["path"]
         walk = os.walk(root) if c.get("include_subdirectories", False) else [(root, [], os.listdir(root))]
         for d, _, files in walk:
             for fn in sorted(files):
-                if fn.lower().endswith(IMAGE_EXT) and not fn.lower().endswith("-masklabel.png"):
+                if fn.lower().endswith(IMAGE_EXT) and not fn.lower().endswith(MASK_POSTFIX):
                     p = os.path.join(d, fn)
-                    out.append((p, _caption(p, c)))
+                    out.append((p, _caption(p, c), mask_path(p)) if masked else (p, _caption(p, c)))
     return out
 
 
@@ -134,15 +156,20 @@ def build_cache(config, model, device, rank: int = 0) -> int:
     def ids(tok, caption):
         return tok(caption, padding="max_length", max_length=77, truncation=True, return_tensors="pt").input_ids[0]
 
+    def row(sample, tokens):
+        r = {"image": Image.open(sample[0]), "tokens": tokens}
+        if len(sample) > 2:   # masked training: the -masklabel.png, one channel (a missing file = all ones)
+            r["mask"] = Image.open(sample[2]).convert("L") if sample[2] else Image.new("L", r["image"].size, 255)
+        return r
+
     if fam in ("sdxl", "flux"):
         enc_text = TE.encode_sdxl_text if fam == "sdxl" else TE.encode_flux_text
         text_fn = lambda t: enc_text(model.text_encoder_1, model.text_encoder_2,  # noqa: E731
                                      t["tokens_1"], t["tokens_2"])
-        rows = ({"image": Image.open(p), "tokens": {"tokens_1": ids(toks[0], c), "tokens_2": ids(toks[1], c)}}
-                for p, c in samples)
+        rows = (row(s, {"tokens_1": ids(toks[0], s[1]), "tokens_2": ids(toks[1], s[1])}) for s in samples)
     else:
         text_fn = lambda t: TE.encode_sd15_text(model.text_encoder_1, t["tokens_1"])  # noqa: E731
-        rows = ({"image": Image.open(p), "tokens": {"tokens_1": ids(toks[0], c)}} for p, c in samples)
+        rows = (row(s, {"tokens_1": ids(toks[0], s[1])}) for s in samples)
     # a generator: each file is opened (and, once decoded, closed) inside the writer's loop, so a concept
     # folder larger than the open-file limit caches
     writer = LatentCacheWriter(lambda im: model.vae_encoder.encode(im), cfg.cache_dir, default_bucketing(cfg),
@@ -164,4 +191,5 @@ def create_data_loader(config, model, device, rank: int = 0, world: int = 1):
                 setattr(model, attr, None)
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
-    return LatentCacheDataLoader(cfg.cache_dir, cfg.batch_size, device, seed=0, rank=rank, world=world)
+    return LatentCacheDataLoader(cfg.cache_dir, cfg.batch_size, device, seed=0, rank=rank, world=world,
+                                 require_mask=bool(getattr(cfg, "masked_training", False)))

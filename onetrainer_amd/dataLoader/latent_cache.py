@@ -8,9 +8,13 @@ The mgds on-disk cache format is not pinned (mgds is not in this image); this bu
   <cache_dir>/index.json            {"version": 1, "samples": [{"file", "crop_resolution"}, ...]}
   <cache_dir>/<i:08d>.safetensors   latent_image [h, w, C] fp32 NHWC (VAE latent_dist.mean, unscaled; C = 4, FLUX.1 16),
                                     original_resolution / crop_offset / crop_resolution int64 [2],
-                                    optional cached text states (text_encoder_*_hidden_state, pooled).
+                                    optional cached text states (text_encoder_*_hidden_state, pooled),
+                                    optional latent_mask [1, h, w] fp32 in [0, 1] (masked training).
 Images are scaled / cropped on the host (data-loader work, as in mgds' worker threads), encoded on
 the GPU by the HIP VAE in same-resolution batches, and written by rank 0 only.
+A sample's mask (masked training: <stem>-masklabel.png, one channel) takes the scale and crop of its image, then
+the downscale to the latent grid (0.125x for the 8x VAEs, StableDiffusionXLBaseDataLoader.py:70) with the same
+antialiased bilinear resize and a clamp to [0, 1].  mgds' exact ScaleImage filter is unpinned (mgds is not in this image).
 The reader yields the reference batch contract (DataLoaderText2ImageMixin._output_modules_from_out_names),
 one resolution per GLOBAL batch, each DP rank taking its slice (aspect_bucketing.rank_slice),
 with one batch prefetched on a host thread into pinned memory.
@@ -41,6 +45,30 @@ def _to_chw01(img) -> torch.Tensor:
     return img.float().contiguous()
 
 
+def _to_mask01(mask) -> torch.Tensor:
+    """PIL image (taken as 'L') / HW uint8 / [1, H, W] float in [0, 1] -> [1, H, W] float32"""
+    if hasattr(mask, "convert"):   # PIL
+        import numpy as np
+        mask = torch.from_numpy(np.asarray(mask.convert("L")).copy())
+    mask = torch.as_tensor(mask)
+    if mask.dtype == torch.uint8:
+        mask = mask.float() / 255.0
+    if mask.dim() == 2:
+        mask = mask[None]
+    if mask.dim() != 3 or mask.shape[0] != 1:
+        raise ValueError(f"mask: one channel expected, got shape {tuple(mask.shape)}")
+    return mask.float().contiguous()
+
+
+def latent_mask(mask: torch.Tensor, scale_res, crop_res, offset, size) -> torch.Tensor:
+    """[1, H, W] mask -> [1, h, w] latent mask: the image's scale_crop, then the downscale to the latent grid
+    `size` -- mgds ScaleImage(factor 0.125) for the 8x VAEs (StableDiffusionXLBaseDataLoader.py:70) -- as the same
+    antialiased bilinear resize, clamped to [0, 1]."""
+    m = scale_crop(mask, scale_res, crop_res, offset)
+    m = F.interpolate(m[None], size=tuple(size), mode="bilinear", antialias=True, align_corners=False)[0]
+    return m.clamp(0.0, 1.0).contiguous()
+
+
 def scale_crop(img: torch.Tensor, scale_res, crop_res, offset):
     """mgds ScaleCropImage: bilinear (antialiased) resize to scale_res, then crop crop_res at offset."""
     x = F.interpolate(img[None], size=tuple(scale_res), mode="bilinear", antialias=True, align_corners=False)[0]
@@ -60,7 +88,8 @@ class LatentCacheWriter:
         self.text_fn = text_fn
 
     def write(self, samples):
-        """samples: iterable of dicts {"image": PIL / tensor, optional "text": {name: tensor}}.
+        """samples: iterable of dicts {"image": PIL / tensor, optional "text": {name: tensor}, optional "mask":
+        PIL 'L' image / HW uint8 / [1, H, W] float in [0, 1], cached as latent_mask}.
         Returns the number of cached samples."""
         os.makedirs(self.cache_dir, exist_ok=True)
         prepared = []
@@ -69,7 +98,9 @@ class LatentCacheWriter:
             h, w = img.shape[1], img.shape[2]
             scale_res, crop_res = self.bucketing.bucket_for(h, w)
             off = crop_offset(scale_res, crop_res)
-            prepared.append((i, img, (h, w), scale_res, crop_res, off, dict(s.get("text") or {}), s.get("tokens")))
+            mask = _to_mask01(s["mask"]) if s.get("mask") is not None else None
+            prepared.append((i, img, (h, w), scale_res, crop_res, off, dict(s.get("text") or {}), s.get("tokens"),
+                             mask))
         by_res: dict = {}
         for p in prepared:
             by_res.setdefault(tuple(p[4]), []).append(p)
@@ -94,6 +125,8 @@ class LatentCacheWriter:
                            "crop_offset": torch.tensor(p[5], dtype=torch.int64),
                            "crop_resolution": torch.tensor(p[4], dtype=torch.int64)}
                     rec.update({k2: v.detach().cpu().contiguous() for k2, v in p[6].items()})
+                    if p[8] is not None:   # on the latent's own grid: crop_res / 8 for the 8x VAEs
+                        rec["latent_mask"] = latent_mask(p[8], p[3], p[4], p[5], l_.shape[:2])
                     fn = f"{i:08d}.safetensors"
                     if self.rank == 0:
                         save_file(rec, os.path.join(self.cache_dir, fn))
@@ -109,13 +142,16 @@ class LatentCacheDataLoader:
     approximate_length(), get_data_loader() iterable of batches on `device`."""
 
     def __init__(self, cache_dir: str, batch_size: int, device, seed: int = 0, rank: int = 0, world: int = 1,
-                 text_defaults: dict | None = None, prefetch: bool = True):
+                 text_defaults: dict | None = None, prefetch: bool = True, require_mask: bool = False):
+        """require_mask (masked training): batches carry latent_mask [B, 1, h, w]; a cached record without
+        one is an error.  Otherwise a cached mask is not emitted."""
         with open(os.path.join(cache_dir, INDEX)) as f:
             self.index = json.load(f)["samples"]
         self.cache_dir, self.batch_size, self.device = cache_dir, batch_size, torch.device(device)
         self.seed, self.rank, self.world, self.epoch = seed, rank, world, -1
         self.text_defaults = text_defaults or {}
         self.prefetch = prefetch
+        self.require_mask = require_mask
         self._batches = []
 
     # BaseDataLoader.get_data_set() -> MGDS-like
@@ -146,6 +182,11 @@ class LatentCacheDataLoader:
         for k, v in self.text_defaults.items():
             if k not in out:
                 out[k] = v.expand(b, *v.shape).contiguous()
+        if self.require_mask:
+            if any("latent_mask" not in r for r in recs):
+                raise ValueError("masked_training: cache was built without masks; delete cache_dir "
+                                 f"({self.cache_dir}) so it is rebuilt with them")
+            out["latent_mask"] = torch.stack([r["latent_mask"] for r in recs])
         out["loss_weight"] = torch.ones(b)
         if torch.cuda.is_available():
             for k, v in list(out.items()):
@@ -176,9 +217,12 @@ class LatentCacheDataLoader:
         q: queue.Queue = queue.Queue(maxsize=2)
 
         def worker():
-            for idx in mine:
-                q.put(self._load(idx))
-            q.put(None)
+            try:
+                for idx in mine:
+                    q.put(self._load(idx))
+                q.put(None)
+            except Exception as e:   # a failed load (e.g. a mask-less cache) is raised by the consumer
+                q.put(e)
 
         t = threading.Thread(target=worker, daemon=True)
         t.start()
@@ -186,6 +230,9 @@ class LatentCacheDataLoader:
             host = q.get()
             if host is None:
                 break
+            if isinstance(host, Exception):
+                t.join()
+                raise host
             yield self._to_device(host)
         t.join()
 

@@ -1497,6 +1497,57 @@ def mse_grad(pred, target, coef, grad_out=None):
     return dpred
 
 
+def _loss_mask(mask, pred):
+    """mask [B, 1, H, W] / [B, H, W] f32 of the latent pixels -> checked, or None"""
+    if mask is None:
+        return None
+    B, H, W, _ = pred.shape
+    _req(mask.dtype == F32 and mask.is_contiguous() and mask.device == pred.device and mask.numel() == B * H * W
+         and mask.shape[0] == B, "loss mask: contiguous f32 [B, 1, H, W] on the prediction's device")
+    return mask
+
+
+def diffusion_loss(pred, target, mask=None, loss_weight=None, mse_strength=1.0, mae_strength=0.0,
+                   log_cosh_strength=0.0, unmasked_weight=0.1, normalize=False, scale=1.0, loss_fn=0, gamma=5.0,
+                   v_pred=False, ga=1.0, timestep=None, coeffs=None, num_t=1000):
+    """mask-weighted MSE + MAE + log-cosh (ModelSetupDiffusionLossMixin.__masked_losses / __unmasked_losses).
+    pred NHWC bf16 [B,H,W,cpad] (first C channels used), target [B,H,W,C], mask f32 [B,1,H,W] or None (unmasked)
+    -> (loss f32[1], coef f32[B,3] (mse, mae, log-cosh), losses f32[B])."""
+    B, H, W, cpad = pred.shape
+    C_ = target.shape[-1]
+    _req(pred.dtype == BF16 and pred.is_contiguous() and target.is_contiguous() and target.shape[:3] == pred.shape[:3]
+         and target.dtype in (F32, BF16), "diffusion_loss shapes")
+    mask = _loss_mask(mask, pred)
+    per = H * W * C_
+    nblk = (per + 2047) // 2048
+    ws = workspace(B * nblk * 4 * 4, pred.device)
+    loss = torch.empty(1, dtype=F32, device=pred.device)
+    coef = torch.empty((B, 3), dtype=F32, device=pred.device)
+    losses = torch.empty(B, dtype=F32, device=pred.device)
+    acp, sq, s1m = coeffs if coeffs is not None else (None, None, None)
+    check(lib().otamd_diffusion_loss(_p(pred), cpad, _p(target), int(target.dtype == F32), _p(mask), B, H * W, C_,
+                                     float(mse_strength), float(mae_strength), float(log_cosh_strength),
+                                     float(unmasked_weight), int(bool(normalize)), float(scale), _p(loss_weight),
+                                     _p(timestep), _p(sq), _p(s1m), int(loss_fn), float(gamma), int(v_pred),
+                                     int(num_t), float(ga), _p(ws), B * nblk * 4, _p(loss), _p(coef), _p(losses),
+                                     stream_handle()), "otamd_diffusion_loss")
+    return loss, coef, losses
+
+
+def diffusion_loss_grad(pred, target, coef, mask=None, unmasked_weight=0.1, grad_out=None):
+    """dpred bf16 [B,H,W,cpad] of diffusion_loss (coef [B,3] from it; the same mask / unmasked_weight)."""
+    B, H, W, cpad = pred.shape
+    C_ = target.shape[-1]
+    _req(pred.dtype == BF16 and pred.is_contiguous() and target.is_contiguous() and target.shape[:3] == pred.shape[:3]
+         and coef.dtype == F32 and coef.is_contiguous() and tuple(coef.shape) == (B, 3), "diffusion_loss_grad shapes")
+    mask = _loss_mask(mask, pred)
+    dpred = torch.empty_like(pred)
+    check(lib().otamd_diffusion_loss_grad(_p(pred), cpad, _p(target), int(target.dtype == F32), _p(mask), B, H * W,
+                                          C_, float(unmasked_weight), _p(coef), _p(grad_out), _p(dpred),
+                                          stream_handle()), "otamd_diffusion_loss_grad")
+    return dpred
+
+
 # ------------------------------------------------------------------------------------------
 # FLUX.1 transformer ops (csrc/flux.hip).  Rows are r = t * B + b; `mod` is the [B, ldm] bf16
 # modulation output (shift / scale / gate chunks at column offsets).

@@ -3,7 +3,7 @@
 Drop-in for modules/modelSetup/BaseFluxSetup.py:193-390 with the math of ModelSetupNoiseMixin
 (noise; LOGIT_NORMAL / UNIFORM timesteps, static or dynamic shift), ModelSetupFlowMatchingMixin.py:14-39
 (sigma = (t + 1) / N, x_t = sigma noise + (1 - sigma) x0), FluxModel.pack/unpack_latents and
-ModelSetupDiffusionLossMixin._flow_matching_losses (unmasked MSE, flow target noise - x0):
+ModelSetupDiffusionLossMixin._flow_matching_losses (MSE, or masked / MAE / log-cosh; flow target noise - x0):
   * latents arrive [B, 16, h, w] (this build's loaders: a view of channels-last storage);
   * one prologue kernel does the shift / scale, the noising and the flow target;
   * the transformer gets t / 1000 and guidance = prior.guidance_scale, like the reference.
@@ -20,7 +20,8 @@ import torch
 from .. import kernels as K
 from ..module import flux_ops as O
 from ..module import functional as Fn
-from .BaseStableDiffusionXLSetup import draw_noise, loss_plan, nhwc_pair, report_learning_rates, timestep_plan
+from .BaseStableDiffusionXLSetup import (draw_noise, loss_mask, loss_plan, nhwc_pair, plain_mse, report_learning_rates,
+                                         timestep_plan)
 from ..util.config.plain import plain
 
 
@@ -102,12 +103,18 @@ class BaseFluxSetup:
                 "target": target.permute(0, 3, 1, 2), "_predicted_nhwc": pred, "_target_nhwc": target}
 
     def calculate_loss(self, model, batch: dict, data: dict, config) -> torch.Tensor:
-        """_flow_matching_losses(...).mean() (BaseFluxSetup.py:377-390): unmasked MSE x loss_weight x scalers."""
+        """_flow_matching_losses(...).mean() (BaseFluxSetup.py:377-390): MSE x loss_weight x scalers on the MSE
+        kernels, or the mask-weighted MSE / MAE / log-cosh family on the unpacked [B, h, w, 16] prediction."""
         plan = loss_plan(plain(config), flow=True)
         lw = batch.get("loss_weight")
         lw = lw.to(self.train_device, torch.float32).contiguous() if lw is not None else None
         pred, target = nhwc_pair(data, 16)
         N = model.noise_scheduler.config["num_train_timesteps"]
-        return Fn.MSELossFn.apply(pred, target, lw, data["timestep"], None, plan["loss_fn"], plan["gamma"], False, 1.0,
-                                  plan["mse_strength"], float(plan["batch_size_scale"] * plan["ga_scale"]),
-                                  1.0 / self.dp_world, N)
+        scale = float(plan["batch_size_scale"] * plan["ga_scale"])
+        if plain_mse(plan):
+            return Fn.MSELossFn.apply(pred, target, lw, data["timestep"], None, plan["loss_fn"], plan["gamma"], False,
+                                      1.0, plan["mse_strength"], scale, 1.0 / self.dp_world, N)
+        strengths = (plan["mse_strength"], plan["mae_strength"], plan["log_cosh_strength"])
+        return Fn.DiffusionLossFn.apply(pred, target, loss_mask(batch, plan, self.train_device), lw, data["timestep"],
+                                        None, plan["loss_fn"], plan["gamma"], False, 1.0, strengths,
+                                        plan["unmasked_weight"], plan["normalize"], scale, 1.0 / self.dp_world, N)

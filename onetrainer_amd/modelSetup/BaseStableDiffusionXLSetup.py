@@ -2,11 +2,13 @@
 
 Drop-in for modules/modelSetup/BaseStableDiffusionXLSetup.py:179-373 (predict, calculate_loss),
 with the math of ModelSetupNoiseMixin.py:18-155, ModelSetupDiffusionMixin.py:15-38 and
-ModelSetupDiffusionLossMixin.py:119-279 done by csrc/diffusion.hip:
+ModelSetupDiffusionLossMixin.py:27-279 done by csrc/diffusion.hip:
   * noise / timesteps: Philox, seeded by the same `batch_seed` (0 if deterministic else
     global_step); counter = index in the GLOBAL batch, so DP rank r draws exactly its slice;
   * DDPM noising + target (epsilon / v_prediction) in one prologue kernel;
-  * unmasked MSE (+ MIN_SNR_GAMMA / DEBIASED_ESTIMATION / P2 weights, loss_weight, scalers).
+  * MSE (+ MIN_SNR_GAMMA / DEBIASED_ESTIMATION / P2 weights, loss_weight, scalers) on the MSE kernels; with
+    masked_training, mae_strength or log_cosh_strength set, the mask-weighted MSE / MAE / log-cosh family
+    (batch["latent_mask"] [B, 1, h, w], ModelSetupDiffusionLossMixin.py:36-117).
 Batch contract as the reference's data loader (StableDiffusionXLBaseDataLoader.py:174-209),
 with `latent_image` [B, 4, h, w]; this build's loaders hand it over as a view of channels-last
 storage, so the kernels' NHWC layout costs no copy.
@@ -27,11 +29,21 @@ TIMESTEP_DIST = {"UNIFORM": 0, "LOGIT_NORMAL": 1}
 
 def loss_plan(config, flow: bool = False) -> dict:
     """The loss decisions of ModelSetupDiffusionLossMixin for this config (config already plain()):
-    batch / GA scale (LossScaler, :243-248 / :290-295) and the timestep weight kernel id (:271-278 for
+    batch / GA scale (LossScaler, :243-248 / :290-295), the timestep weight kernel id (:271-278 for
     DDPM: MIN_SNR_GAMMA / DEBIASED_ESTIMATION / P2, anything else unweighted; :316-319 for flow
-    matching: SIGMA, anything else unweighted)."""
-    if config.mae_strength != 0 or config.log_cosh_strength != 0 or config.masked_training:
-        raise NotImplementedError("only the unmasked MSE loss of C1-C5 is on this build's hot path")
+    matching: SIGMA, anything else unweighted), the MSE / MAE / log-cosh strengths (:47-99,130-150) and the
+    mask terms of masked training (:258-261, masked_loss.py:21-37).  The mask fields are read only under
+    masked_training, with the reference's defaults (TrainConfig.py:933-938) where a config lacks them.
+    vb_loss_strength is not read: the reference applies that term only when the model predicts variance
+    values (:102,153), which SD / SDXL / FLUX never do."""
+    masked = bool(config.masked_training)
+    unmasked_weight, normalize = 0.1, False
+    if masked:
+        if float(getattr(config, "masked_prior_preservation_weight", 0.0)) != 0:
+            raise NotImplementedError("masked_prior_preservation_weight != 0: the prior-preservation term needs a "
+                                      "prior_target, which predict() does not produce")
+        unmasked_weight = float(getattr(config, "unmasked_weight", 0.1))
+        normalize = bool(getattr(config, "normalize_masked_area_loss", False))
     scaler = config.loss_scaler
     if scaler not in ("NONE", "BATCH", "GRADIENT_ACCUMULATION", "BOTH"):
         raise ValueError(f"loss_scaler {scaler!r}")
@@ -43,7 +55,25 @@ def loss_plan(config, flow: bool = False) -> dict:
     else:
         kid = LOSS_FN.get(fn, 0)
     return {"batch_size_scale": bs, "ga_scale": gas, "loss_fn": kid, "gamma": float(config.loss_weight_strength),
-            "mse_strength": float(config.mse_strength)}
+            "mse_strength": float(config.mse_strength), "mae_strength": float(config.mae_strength),
+            "log_cosh_strength": float(config.log_cosh_strength), "masked": masked,
+            "unmasked_weight": unmasked_weight, "normalize": normalize}
+
+
+def plain_mse(plan: dict) -> bool:
+    """the plan is the unmasked MSE alone: the loss stays on the MSE kernels"""
+    return not plan["masked"] and plan["mae_strength"] == 0 and plan["log_cosh_strength"] == 0
+
+
+def loss_mask(batch: dict, plan: dict, device):
+    """batch["latent_mask"] [B, 1, h, w] as the loss kernel reads it (f32, contiguous, on the device), or None
+    when the plan is unmasked"""
+    if not plan["masked"]:
+        return None
+    if "latent_mask" not in batch:
+        raise KeyError("latent_mask: masked_training is on, but the batch carries no 'latent_mask' "
+                       "(a cache built without masks?)")
+    return batch["latent_mask"].to(device, torch.float32).contiguous()
 
 
 def timestep_plan(config) -> int:
@@ -199,7 +229,13 @@ class BaseStableDiffusionXLSetup:
         lw = batch.get("loss_weight")
         lw = lw.to(self.train_device, torch.float32).contiguous() if lw is not None else None
         pred, target = nhwc_pair(data, 4)
-        return Fn.MSELossFn.apply(pred, target, lw, data["timestep"], model.noise_scheduler.coeffs, plan["loss_fn"],
-                                  plan["gamma"], data.get("prediction_type") == "v_prediction", 1.0,
-                                  plan["mse_strength"], float(plan["batch_size_scale"] * plan["ga_scale"]),
-                                  1.0 / self.dp_world)
+        v_pred = data.get("prediction_type") == "v_prediction"
+        scale = float(plan["batch_size_scale"] * plan["ga_scale"])
+        if plain_mse(plan):
+            return Fn.MSELossFn.apply(pred, target, lw, data["timestep"], model.noise_scheduler.coeffs, plan["loss_fn"],
+                                      plan["gamma"], v_pred, 1.0, plan["mse_strength"], scale, 1.0 / self.dp_world)
+        strengths = (plan["mse_strength"], plan["mae_strength"], plan["log_cosh_strength"])
+        return Fn.DiffusionLossFn.apply(pred, target, loss_mask(batch, plan, self.train_device), lw, data["timestep"],
+                                        model.noise_scheduler.coeffs, plan["loss_fn"], plan["gamma"], v_pred, 1.0,
+                                        strengths, plan["unmasked_weight"], plan["normalize"], scale,
+                                        1.0 / self.dp_world)

@@ -606,3 +606,31 @@ class MSELossFn(torch.autograd.Function):
         if ctx.grad_scale != 1.0:   # data-parallel: fold 1/world into the loss gradient (sum all-reduce = mean)
             gd = gd * ctx.grad_scale
         return (K.mse_grad(pred, target, coef, grad_out=gd.contiguous()),) + (None,) * 12
+
+
+class DiffusionLossFn(torch.autograd.Function):
+    """ModelSetupDiffusionLossMixin.__masked_losses / __unmasked_losses with the MSE, MAE and log-cosh terms
+    + _diffusion_losses / _flow_matching_losses + .mean() (+ /GA).  mask: f32 [B, 1, h, w] or None (unmasked)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, loss_weight, timestep, coeffs, loss_fn, gamma, v_pred, ga, strengths,
+                unmasked_weight, normalize, scale, grad_scale=1.0, num_t=1000):
+        mse_s, mae_s, lc_s = strengths
+        loss, coef, losses = K.diffusion_loss(pred, target, mask, loss_weight, mse_strength=mse_s, mae_strength=mae_s,
+                                              log_cosh_strength=lc_s, unmasked_weight=unmasked_weight,
+                                              normalize=normalize, scale=scale, loss_fn=loss_fn, gamma=gamma,
+                                              v_pred=v_pred, ga=ga, timestep=timestep, coeffs=coeffs, num_t=num_t)
+        ctx.save_for_backward(pred, target, coef, *(() if mask is None else (mask,)))
+        ctx.losses = losses
+        ctx.unmasked_weight = unmasked_weight
+        ctx.grad_scale = grad_scale
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, coef, *mask = ctx.saved_tensors
+        gd = g.reshape(1).float()
+        if ctx.grad_scale != 1.0:   # data-parallel: fold 1/world into the loss gradient (sum all-reduce = mean)
+            gd = gd * ctx.grad_scale
+        return (K.diffusion_loss_grad(pred, target, coef, mask[0] if mask else None, ctx.unmasked_weight,
+                                      grad_out=gd.contiguous()),) + (None,) * 15

@@ -80,6 +80,12 @@ class TrainConfig:
     loss_weight_strength: float = 5.0
     loss_scaler: str = "NONE"
     masked_training: bool = False
+    # masked training (TrainConfig.py:933-938); unmasked_probability is read by the reference's inpainting
+    # loaders only and masked_prior_preservation_weight != 0 is refused (modelSetup loss_plan)
+    unmasked_probability: float = 0.1
+    unmasked_weight: float = 0.1
+    normalize_masked_area_loss: bool = False
+    masked_prior_preservation_weight: float = 0.0
     # LoRA
     lora_rank: int = 16
     lora_alpha: float = 1.0
