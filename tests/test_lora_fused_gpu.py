@@ -36,6 +36,19 @@ def two_launch_split1(monkeypatch, fn):
         return fn()
 
 
+def fused_launch(monkeypatch, fn):
+    """fn(): a `tile=` call, which must run as the one fused launch.  When the launcher refuses the tile the wrappers
+    quietly issue the two-launch form instead (and the test would compare that form with itself): on the ctypes host
+    path both of its GEMMs go through kernels._gemm, which must not be reached."""
+    calls = []
+    gemm = K._gemm
+    with monkeypatch.context() as m, K.python_host():
+        m.setattr(K, "_gemm", lambda a, s, d: (calls.append((a.M, a.N, a.K)), gemm(a, s, d))[1])
+        out = fn()
+    assert not calls, f"the fused form fell back to separate launches: {calls}"
+    return out
+
+
 @pytest.mark.parametrize("tile", [1, 4, 7, 8])
 @pytest.mark.parametrize("M,Kd,P,pw,epi", [(1000, 640, 1, 640, True), (4096, 1280, 3, 1280, False),
                                            (300, 1280, 2, 1280, True)])
@@ -49,7 +62,7 @@ def test_linear_lora_fused_bitwise(dev, monkeypatch, tile, M, Kd, P, pw, epi):
     b = rnd(P * pw, dev=dev) if epi else None
     res = rnd(M, P * pw, dev=dev) if epi else None
     t = torch.full((M, P * r), float("nan"), device=dev, dtype=BF)
-    y = K.linear_lora(x, w, b, res, down, up2, t, r, pw, tile=tile)
+    y = fused_launch(monkeypatch, lambda: K.linear_lora(x, w, b, res, down, up2, t, r, pw, tile=tile))
 
     def ref():
         t_ref = K.linear(x, down)
@@ -79,7 +92,8 @@ def test_conv_lora_fused_bitwise(dev, monkeypatch, tile, N, H, W, Cin, Cout, str
     P, Q = K.conv_out_hw(H, W, 3, stride, 1, up)
     rowvec = rnd(N, Cout, dev=dev)
     t = torch.empty((N, P, Q, r), device=dev, dtype=BF)
-    y = K.conv2d_lora(x, w, b, stride, 1, up, None, rowvec, down, up2, t, r, tile=tile)
+    y = fused_launch(monkeypatch,
+                     lambda: K.conv2d_lora(x, w, b, stride, 1, up, None, rowvec, down, up2, t, r, tile=tile))
 
     def ref():
         t_ref = K.conv2d(x, down, stride=stride, pad=1, upsample=up)
@@ -135,7 +149,7 @@ def test_linear_dgrad_lora_fused_bitwise(dev, monkeypatch, tile, M, Nout, Kin):
     up2, down = rnd(Nout, r, dev=dev, scale=0.05), rnd(r, Kin, dev=dev, scale=0.05)
     upT, downT = up2.t().contiguous(), down.t().contiguous()
     u = torch.full((M, r), float("nan"), device=dev, dtype=BF)
-    dx = K.linear_dgrad_lora(dy, w, up2, down, upT, downT, u, tile=tile)
+    dx = fused_launch(monkeypatch, lambda: K.linear_dgrad_lora(dy, w, up2, down, upT, downT, u, tile=tile))
 
     def ref():
         u_ref = K.linear_dgrad(dy, up2)
@@ -211,7 +225,7 @@ def test_linear_dgrad_lora_fused_qkv_bitwise(dev, monkeypatch, tile, M, pw, Kin)
     upT = torch.cat([up2[p * pw:(p + 1) * pw, p * r:(p + 1) * r].t() for p in range(P)], dim=1).contiguous()
     downT = down.t().contiguous()
     u = torch.full((M, P * r), float("nan"), device=dev, dtype=BF)
-    dx = K.linear_dgrad_lora(dy, w, up2, down, upT, downT, u, tile=tile)
+    dx = fused_launch(monkeypatch, lambda: K.linear_dgrad_lora(dy, w, up2, down, upT, downT, u, tile=tile))
 
     def ref():
         u_ref = K.linear_dgrad(dy, up2)
