@@ -2,20 +2,7 @@
 // 256-wide LDS-DMA kernels).  GemmArgs is passed by value to the kernels and through the C ABI.
 #pragma once
 #include "common.h"
-
-// OPM_CONV_WT (v2 only): B of conv dgrad read straight from the stored weight W[Cout][KH][KW][Cin] as
-// an MN-mode operand B[k = tap*Cout + co][ci] (row address (co*KK + tap)*ld); gb.SC = Cout, gb.KH/KW.
-enum { OPM_K = 0, OPM_MN = 1, OPM_CONV_FWD = 2, OPM_CONV_DGRAD = 3, OPM_CONV_WGRAD = 4, OPM_CONV_WT = 5 };
-
-struct ConvGeom {
-  int N;             // batch
-  int SH, SW, SC;    // gathered (source) tensor: spatial dims and channel count
-  int RH, RW;        // spatial dims decoding a GEMM row index (fwd: output, dgrad: input, wgrad: output)
-  int KH, KW, stride, pad;
-  int upsample;      // source read through a virtual nearest-2x upsample (fwd / wgrad)
-  int pad_;
-  long long ld;      // pixel stride of the source, elements
-};
+#include "gemm2_stage.h"   // operand modes (OPM_*), ConvGeom, the MN-mode LDS swizzle
 
 struct GemmArgs {
   const bf16_t* A; long long lda; int amode;
@@ -179,14 +166,7 @@ __device__ __forceinline__ void tile_coords(int wg, int tiles_m, int tiles_n, in
 
 // K-mode LDS image: [rows][64 k], 128-byte rows, 16-byte chunk c of row r stored at c ^ (r & 7)
 __device__ __forceinline__ int kimg_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-// MN-mode LDS image: [64 k rows][RB bytes], 32-byte block b of row k stored at b ^ s(k)
-__device__ __forceinline__ int mn_swz(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-// the same for an image of RB-byte rows: a 64-wide tile (128-byte rows) has only 4 blocks per row
-// and 160-wide tiles (320-byte rows, 10 blocks): the 80-dword row pitch already spreads rows k..k+3 over
-// four 8-bank groups; rows k+8.. alias them, so block bit 0 flips with k bit 3 (stays inside the row)
-template <int RB> __device__ __forceinline__ int mn_swz_rb(int k) {
-  return RB == 320 ? ((k >> 3) & 1) : (RB >= 256 ? mn_swz(k) : (k & 3));
-}
+// MN-mode LDS image: [64 k rows][RB bytes], 32-byte block b of row k stored at b ^ mn_swz_rb<RB>(k) (gemm2_stage.h)
 
 // alpha * sum_s slab[s] (+bias, +rowvec, +residual) (+C if accumulate) for V consecutive columns
 // n.. of row m: the split-K combine of splitk_reduce_kernel (splits summed in index order).

@@ -15,6 +15,7 @@
 //     flight across the barrier while the current one is multiplied.
 #pragma once
 #include "gemm.h"
+#include "gemm2_stage.h"
 
 // Timing ablations of the K loop (tools/gemm_ablate.sh builds them as separate libraries; results are garbage):
 //   1 = no DMA after the prologue, 2 = no MFMA (fragments kept live), 3 = no fragment reads after the prologue,
@@ -25,7 +26,6 @@
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) short4v lds_s4_t;
-#define OFF_INVALID 0x80000000u
 
 #define MEMBAR() asm volatile("" ::: "memory")
 #define BARRIER()                      \
@@ -50,68 +50,24 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds, unsi
   asm volatile("buffer_load_dwordx4 %1, %2, 0 offen lds" ::"{m0}"(m0), "v"(off), "s"(rs) : "memory");
 }
 
-template <int MODE> struct IsKMode {
-  static constexpr bool v = (MODE == OPM_K || MODE == OPM_CONV_FWD || MODE == OPM_CONV_DGRAD);
-};
-
-// Per-lane DMA state of one operand tile (BMN rows/cols x 64 k): BMN/8 pieces of 1 KiB, NW waves
-// take NI = BMN/(8 NW) each (piece j = wave + NW i).
-template <int MODE, int BMN, int NW>
-struct Stage {
-  static constexpr bool KM = IsKMode<MODE>::v;
-  static constexpr int NP = BMN / 8;                  // 1 KiB pieces per stage image
-  static constexpr int NI = (NP + NW - 1) / NW;       // pieces per wave (the last may be absent)
-  static constexpr bool EVEN = NP % NW == 0;          // 160-wide images: 20 pieces over 8 waves
-  static constexpr int RB = BMN * 2;      // MN-mode row bytes
-  int a[NI], b[NI], c[NI];                // K: (row elem offset | conv n,y0,x0) ; MN: (k row, col, -)
-  int t0, t1, t2;                         // K: logical chunk ; MN-conv: per-piece decode lives in a/b/c
-  bool ok[NI];
-
-  __device__ __forceinline__ void prepare(const ConvGeom& g, long long ld, int mn0, int MNsz, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int j = wave + NW * i;
-      if constexpr (KM) {
-        const int r = 8 * j + (lane >> 3);
-        const int gm = mn0 + r;
-        ok[i] = gm < MNsz;
-        if constexpr (MODE == OPM_K) {
-          a[i] = gm * (int)ld;
-        } else {
-          const int rr = ok[i] ? gm : 0;
-          const int hw = g.RH * g.RW;
-          const int n = rr / hw, rem = rr - n * hw;
-          const int y = rem / g.RW, x = rem - y * g.RW;
-          a[i] = n;
-          if constexpr (MODE == OPM_CONV_FWD) { b[i] = y * g.stride - g.pad; c[i] = x * g.stride - g.pad; }
-          else { b[i] = y + g.pad; c[i] = x + g.pad; }
-        }
-      } else {
-        const int byte = j * 1024 + lane * 16;
-        const int r = byte / RB;
-        const int pc = (byte % RB) >> 4;
-        const int lb = (pc >> 1) ^ mn_swz_rb<RB>(r);
-        const int col = mn0 + (lb * 2 + (pc & 1)) * 8;
-        a[i] = r;
-        ok[i] = col < MNsz;
-        if constexpr (MODE == OPM_MN || MODE == OPM_CONV_WT) {
-          b[i] = col;
-        } else {   // OPM_CONV_WGRAD: col = (tap, ch)
-          const int cc = ok[i] ? col : 0;
-          const int tap = cc / g.SC;
-          c[i] = cc - tap * g.SC;
-          b[i] = tap;
-        }
-      }
-    }
-    if constexpr (KM) t0 = (lane & 7) ^ ((lane >> 3) & 7);
+// One operand tile's DMA: the index decode of gemm2_stage.h (StageIndex) plus the issue of its pieces.  The conv
+// gathers carry their decode from K-step to K-step (offsets_step: no division in the K loop), so their tiles must be
+// issued in K order from the split's first (start()).
+// INC = false keeps a conv gather on the closed form: the three instances whose register allocation the carried state
+// tipped over a limit (conv_inc_a / conv_inc_b below).
+template <int MODE, int BMN, int NW, bool INC = true>
+struct Stage : StageIndex<MODE, BMN, NW> {
+  using SI = StageIndex<MODE, BMN, NW>;
+  using SI::NI; using SI::NP; using SI::EVEN;
+  static constexpr bool CONV = SI::CONV && INC;
+  __device__ __forceinline__ void start(const ConvGeom& g, int kbeg) {
+    if constexpr (CONV) SI::start(g, kbeg);
   }
-
-  // source byte offset of this wave's piece i of the K tile at k0, any mode: offsets() for one piece; with i a compile-time index the other
-  // pieces' arithmetic is dead and dropped
+  // source byte offset of this wave's piece i of the K tile at k0 (plain K / MN operands): offsets() for one piece; with i a compile-time
+  // index the other pieces' arithmetic is dead and dropped
   __device__ __forceinline__ unsigned offset_g(const ConvGeom& g, long long ld, int k0, int Kend, int i) const {
     unsigned tmp[NI];
-    offsets(g, ld, k0, Kend, tmp);
+    SI::offsets(g, ld, k0, Kend, tmp);
     return tmp[i];
   }
   // this wave's piece i of the image at img (piece j = wave + NW i); absent pieces of an uneven image are skipped
@@ -121,75 +77,10 @@ struct Stage {
   __device__ __forceinline__ void issue(__amdgpu_buffer_rsrc_t rs, char* img, const ConvGeom& g, long long ld, int k0,
                                         int Kend, int wave) {
     unsigned off[NI];
-    offsets(g, ld, k0, Kend, off);
+    if constexpr (CONV) SI::offsets_step(g, ld, k0, Kend, off);
+    else SI::offsets(g, ld, k0, Kend, off);
 #pragma unroll
     for (int i = 0; i < NI; ++i) put(rs, img, wave, i, off[i]);
-  }
-  // source byte offsets of this wave's pieces of the K tile at k0 (OFF_INVALID: zero-fill)
-  __device__ __forceinline__ void offsets(const ConvGeom& g, long long ld, int k0, int Kend, unsigned (&out)[NI]) const {
-    if constexpr (KM) {
-      const int k = k0 + 8 * t0;
-      const bool kok = k < Kend;
-      int r_ = 0, s_ = 0, ch = 0;
-      if constexpr (MODE != OPM_K) {
-        const int tap = kok ? k / g.SC : 0;
-        ch = k - tap * g.SC;
-        r_ = tap / g.KW;
-        s_ = tap - r_ * g.KW;
-      }
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        unsigned off = OFF_INVALID;
-        if constexpr (MODE == OPM_K) {
-          if (kok && ok[i]) off = (unsigned)(a[i] + k) * 2u;
-        } else {
-          bool v = kok && ok[i];
-          int sy, sx;
-          if constexpr (MODE == OPM_CONV_FWD) {
-            const int y = b[i] + r_, x = c[i] + s_;
-            if (g.upsample) { v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
-            else { v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
-          } else {
-            const int ty = b[i] - r_, tx = c[i] - s_;
-            if (g.stride == 1) { sy = ty; sx = tx; }
-            else {
-              v = v && ty >= 0 && tx >= 0 && (ty % g.stride) == 0 && (tx % g.stride) == 0;
-              sy = ty / g.stride; sx = tx / g.stride;
-            }
-            v = v && sy >= 0 && sy < g.SH && sx >= 0 && sx < g.SW;
-          }
-          if (v) off = (unsigned)(((a[i] * g.SH + sy) * g.SW + sx) * (int)g.ld + ch) * 2u;
-        }
-        out[i] = off;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int k = k0 + a[i];
-        unsigned off = OFF_INVALID;
-        if constexpr (MODE == OPM_MN) {
-          if (ok[i] && k < Kend) off = (unsigned)(k * (int)ld + b[i]) * 2u;
-        } else if constexpr (MODE == OPM_CONV_WT) {   // k = tap*Cout + co -> W row co*KK + tap
-          if (ok[i] && k < Kend) {
-            const int tap = k / g.SC, co = k - tap * g.SC;
-            off = (unsigned)((co * (g.KH * g.KW) + tap) * (int)ld + b[i]) * 2u;
-          }
-        } else {   // conv wgrad: k = output pixel
-          bool v = ok[i] && k < Kend;
-          const int kk = v ? k : 0;
-          const int hw = g.RH * g.RW;
-          const int n = kk / hw, rem = kk - n * hw;
-          const int p = rem / g.RW, q = rem - p * g.RW;
-          const int tr = b[i] / g.KW, ts = b[i] - (b[i] / g.KW) * g.KW;
-          const int y = p * g.stride - g.pad + tr, x = q * g.stride - g.pad + ts;
-          int sy, sx;
-          if (g.upsample) { v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
-          else { v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
-          if (v) off = (unsigned)(((n * g.SH + sy) * g.SW + sx) * (int)g.ld + c[i]) * 2u;
-        }
-        out[i] = off;
-      }
-    }
   }
 };
 
@@ -292,10 +183,16 @@ __global__ void __launch_bounds__(NW * 64, (LDR == 0 && NS == 2 && BM == 128 && 
 
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)args.A, (short)0, (int)a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)args.B, (short)0, (int)b_bytes, 0x00020000);
-  Stage<AM, BM, NW> sa;
-  Stage<BMODE, BN, NW> sb;
+  // closed-form gathers, from profiles/conv_index_static.md: the carried state cost conv fwd 256x160 its third wave
+  // (168 -> 170 VGPRs), wgrad 128x64 its eighth (64 -> 65) and the 128x160 colsum wgrad 20 more bytes of scratch
+  constexpr bool conv_inc_a = !(AM == OPM_CONV_FWD && BM == 256 && BN == 160 && !SEG2 && !LD);
+  constexpr bool conv_inc_b = !(BMODE == OPM_CONV_WGRAD && BM == 128 && ((BN == 160 && CS) || (BN == 64 && !CS)));
+  Stage<AM, BM, NW, conv_inc_a> sa;
+  Stage<BMODE, BN, NW, conv_inc_b> sb;
   sa.prepare(args.ga, args.lda, m0, args.M, wave, lane);
   sb.prepare(args.gb, args.ldb, n0, args.N, wave, lane);
+  sa.start(args.ga, kbeg);   // conv gathers: the decode of the split's first K tile, carried from there
+  sb.start(args.gb, kbeg);
   // second K segment: A2 always K-mode; B2 in the LDS image mode of B
   constexpr int B2M = BKm ? OPM_K : OPM_MN;
   Stage<OPM_K, SEG2 ? BM : 64 * NW / 8, NW> sa2;
@@ -384,9 +281,10 @@ __global__ void __launch_bounds__(NW * 64, (LDR == 0 && NS == 2 && BM == 128 && 
   // at dst placed one after each read: the inline-asm DMA keeps its place among the DS reads (both touch memory)
   // while interleave()'s groups put the MFMAs between the reads
   constexpr int NIA = Stage<AM, BM, NW>::NI, NIB = Stage<BMODE, BN, NW>::NI;
-  // plain K / MN operands only: with a conv gather the per-piece offset arithmetic (integer divisions) inside phase B
-  // cost more than the burst (conv fwd / dgrad 10-15 % slower, profiles/r4_gemm_spread_conv_*), and the 128-row
-  // colsum tiles (at their 128-VGPR cap) spilled 15 registers
+  // plain K / MN operands only: with a conv gather the per-piece offset arithmetic (integer divisions, then) inside
+  // phase B cost more than the burst (conv fwd / dgrad 10-15 % slower, profiles/r4_gemm_spread_conv_*; not measured
+  // again since the gathers carry their indices), and the 128-row colsum tiles (at their 128-VGPR cap) spilled 15
+  // registers
   // The LoRA second segment (SEG2) spreads the refills of its first segment too; the few refills that land in the
   // second segment (K2 <= 64 rows: one K-step) go out as a burst through issue_tile.  Not the 128x160 dgrad form with
   // a second segment: at its 128-VGPR cap the spread pushed it to 20 bytes of scratch per lane.
