@@ -104,6 +104,19 @@ typedef struct AdamwGroup {
 
 typedef struct NormChunk { long long begin, end; int tensor, pad; } NormChunk;
 
+/* Adafactor tables (csrc/adafactor.hip describes the modes and the slab layout) */
+typedef struct AdafactorTensor {
+  long long offset, numel;
+  long long row_off, col_off, full_off;
+  long long rpart_off, cpart_off, rmean_off;
+  int batch, rows, cols, mode, group, slab_rows, row_slabs, col_tiles, slab0, n_slabs, pad0, pad1;
+} AdafactorTensor;
+typedef struct AdafactorSlab { long long row0, row1; int tensor, col0, col1, pad; } AdafactorSlab;
+typedef struct AdafactorGroup {
+  float lr, neg_wd, alpha_wd, eps1, eps2, clip_threshold, beta2t, one_minus_beta2t;
+  int scale_parameter, pad;
+} AdafactorGroup;
+
 /* replaces: diffusers Linear/Conv2d fwd+bwd inside model.unet(...) (modules/modelSetup/BaseStableDiffusionXLSetup.py:268-273); conv/linear dgrad/wgrad of loss.backward() (modules/trainer/GenericTrainer.py:693-696) */
 int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long long ws_bytes, hipStream_t stream);
 
@@ -484,6 +497,26 @@ int otamd_grad_clip_finalize(const void* chunks, int n_chunks, const double* chu
 
 /* replaces: the grad scaling half of clip_grad_norm_ when not fused into AdamW */
 int otamd_scale_bf16_by_device_scalar(void* g, long long n, const float* coef, hipStream_t stream);
+
+/* replaces: transformers.Adafactor + patch_adafactor (modules/util/create.py:914-936), its step
+   step_adafactor_parameter (modules/util/optimizer/adafactor_extensions.py:16-95) for every tensor [t_begin, t_end)
+   of the table and their slabs [s_begin, s_end): factored second moments for ndim >= 2 (the last two dimensions are
+   the matrix), a full second moment otherwise, update clipping by rms(u) / clip_threshold, lr * max(eps2, rms(p))
+   with scale_parameter, weight decay.  form 0: p, g bf16 (round-to-nearest, or stochastic with the AdamW dither);
+   1: p, g fp32; 2: p the fp32 master, g bf16, w16 the bf16 working copy rewritten as rne(p).  state: fp32 row /
+   column / full states; scratch: fp32 partial sums; slab_sq: double[2 * slabs]; scal: float[4 * tensors] (rms(p),
+   rms(u)); clip_coef: the pending global-norm clip (device scalar, nullable).  Five launches, no atomics. */
+int otamd_adafactor_step(void* p, const void* g, void* w16, int form, float* state, float* scratch, double* slab_sq,
+    float* scal, const void* tensors, int t_begin, int t_end, const void* slabs, int s_begin, int s_end,
+    const AdafactorGroup* groups, int n_groups, const float* clip_coef, int stochastic_rounding,
+    unsigned long long seed, hipStream_t stream);
+
+/* replaces: ABI check */
+int otamd_adafactor_tensor_size(void);
+/* replaces: ABI check */
+int otamd_adafactor_slab_size(void);
+/* replaces: ABI check */
+int otamd_adafactor_group_size(void);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,26 @@ class NormChunk(C.Structure):
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("tensor", C.c_int), ("pad", C.c_int)]
 
 
+class AdafactorTensor(C.Structure):
+    _fields_ = [("offset", C.c_longlong), ("numel", C.c_longlong), ("row_off", C.c_longlong),
+                ("col_off", C.c_longlong), ("full_off", C.c_longlong), ("rpart_off", C.c_longlong),
+                ("cpart_off", C.c_longlong), ("rmean_off", C.c_longlong),
+                ("batch", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("mode", C.c_int), ("group", C.c_int),
+                ("slab_rows", C.c_int), ("row_slabs", C.c_int), ("col_tiles", C.c_int), ("slab0", C.c_int),
+                ("n_slabs", C.c_int), ("pad0", C.c_int), ("pad1", C.c_int)]
+
+
+class AdafactorSlab(C.Structure):
+    _fields_ = [("row0", C.c_longlong), ("row1", C.c_longlong), ("tensor", C.c_int), ("col0", C.c_int),
+                ("col1", C.c_int), ("pad", C.c_int)]
+
+
+class AdafactorGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("neg_wd", C.c_float), ("alpha_wd", C.c_float), ("eps1", C.c_float),
+                ("eps2", C.c_float), ("clip_threshold", C.c_float), ("beta2t", C.c_float),
+                ("one_minus_beta2t", C.c_float), ("scale_parameter", C.c_int), ("pad", C.c_int)]
+
+
 class LoraShadowEntry(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("rows", C.c_int), ("cols", C.c_int),
                 ("dst_ld", C.c_int), ("scale", C.c_float), ("transpose", C.c_int), ("pad", C.c_int)]
@@ -104,6 +124,12 @@ SIGNATURES: dict[str, list] = {
     "otamd_grad_sqnorm_chunks": [VP, I, VP, I, I, VP, VP],
     "otamd_grad_clip_finalize": [VP, I, VP, VP, I, F, I, VP, VP],
     "otamd_scale_bf16_by_device_scalar": [VP, LL, VP, VP],
+    # adafactor.hip
+    "otamd_adafactor_step": [VP, VP, VP, I, VP, VP, VP, VP, VP, I, I, VP, I, I, C.POINTER(AdafactorGroup), I, VP, I,
+                             C.c_ulonglong, VP],
+    "otamd_adafactor_tensor_size": [],
+    "otamd_adafactor_slab_size": [],
+    "otamd_adafactor_group_size": [],
     # norm.hip
     "otamd_groupnorm_fwd": [VP, LL, VP, LL, I, I, I, I, F, VP, VP, I, VP, VP, VP, VP, VP, VP],
     "otamd_groupnorm_bwd": [VP, LL, VP, LL, VP, LL, I, I, I, I, VP, I, VP, VP, VP, VP, VP, VP, I, I, VP, I, VP],
@@ -224,3 +250,6 @@ def check_layouts():
     assert L.otamd_attn_args_size() == C.sizeof(AttnArgs), (L.otamd_attn_args_size(), C.sizeof(AttnArgs))
     assert L.otamd_lora_shadow_entry_size() == C.sizeof(LoraShadowEntry)
     assert L.otamd_qk_rope_args_size() == C.sizeof(QKRopeArgs), (L.otamd_qk_rope_args_size(), C.sizeof(QKRopeArgs))
+    assert L.otamd_adafactor_tensor_size() == C.sizeof(AdafactorTensor)
+    assert L.otamd_adafactor_slab_size() == C.sizeof(AdafactorSlab)
+    assert L.otamd_adafactor_group_size() == C.sizeof(AdafactorGroup)

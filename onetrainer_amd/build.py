@@ -28,6 +28,7 @@ ARCH = "gfx950"
 # so no fp contraction beyond the explicit fmaf calls
 EXTRA = {
     "adamw.hip": ["-ffp-contract=off"],
+    "adafactor.hip": ["-ffp-contract=off"],
     "diffusion.hip": ["-ffp-contract=off"],
     # no NaN canonicalisation (v_max_f32 x, x) in front of every fmaxf on an MFMA result: one extra
     # VALU per softmax score; the kernels never produce or test NaNs (masked keys are -inf)

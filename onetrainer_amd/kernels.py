@@ -874,6 +874,37 @@ def adamw_master(p32, g, m32, v32, w, groups, clip_coef=None, begin=0, end=None)
           "otamd_adamw_master_range")
 
 
+def adafactor_step(p, g, w, state, scratch, slab_sq, scal, tensors_dev, t_range, slabs_dev, s_range, groups,
+                   clip_coef=None, stochastic_rounding=False, seed=0):
+    """one fused Adafactor step (csrc/adafactor.hip) over the tensors t_range and slabs s_range of the device tables.
+    p / g: the flat store and its gradients (bf16 / bf16, fp32 / fp32, or the fp32 master with bf16 gradients and
+    the bf16 working copy w).  The tables name element ranges of these buffers: the caller built and checked them
+    (util/optimizer/adafactor_fused.py)."""
+    n = p.numel()
+    _req(p.dtype in (BF16, F32) and g.dtype in (BF16, F32), "adafactor flat buffers: bf16 or fp32")
+    if w is not None:
+        form = 2
+        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, "adafactor master: fp32 p, bf16 g and w")
+    else:
+        form = 0 if p.dtype == BF16 else 1
+        _req(g.dtype == p.dtype, "adafactor: gradients in the store's dtype")
+    for t in (p, g) + ((w,) if w is not None else ()):
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "adafactor flat buffers")
+    for t in (state, scratch, scal):
+        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), "adafactor fp32 buffers")
+    _req(slab_sq.is_cuda and slab_sq.dtype == torch.float64 and slab_sq.numel() * 16 >= slabs_dev.numel(), "slab_sq f64")
+    _req(scal.numel() * C.sizeof(_lib.AdafactorTensor) >= 4 * tensors_dev.numel(), "scal f32[4 * tensors]")
+    nt, ns = tensors_dev.numel() // C.sizeof(_lib.AdafactorTensor), slabs_dev.numel() // C.sizeof(_lib.AdafactorSlab)
+    _req(0 <= t_range[0] <= t_range[1] <= nt and 0 <= s_range[0] <= s_range[1] <= ns, "adafactor table ranges")
+    _req(1 <= len(groups) <= 8, "adafactor: 1..8 parameter groups")
+    arr = (_lib.AdafactorGroup * len(groups))(*groups)
+    check(lib().otamd_adafactor_step(_p(p), _p(g), _p(w), form, _p(state), _p(scratch), _p(slab_sq), _p(scal),
+                                     _p(tensors_dev), t_range[0], t_range[1], _p(slabs_dev), s_range[0], s_range[1],
+                                     arr, len(groups), _p(clip_coef), int(stochastic_rounding),
+                                     seed & 0xFFFFFFFFFFFFFFFF, stream_handle()),
+          "otamd_adafactor_step")
+
+
 def grad_norm_dtype(grads, fp32_semantics=False):
     """the C-ABI grad_dtype code: 0 bf16, 1 fp32, 2 bf16 storage of an fp32-master network's gradients."""
     if grads.dtype == BF16:

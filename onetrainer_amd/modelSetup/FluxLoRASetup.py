@@ -9,7 +9,7 @@ import torch
 from ..util.dtype_util import dtype_plan
 from ..module.lora import LoRAWrapper
 from ..util.NamedParameterGroup import NamedParameterGroup, NamedParameterGroupCollection
-from ..util.optimizer.adamw_fused import FusedAdamW
+from ..util.create import create_optimizer
 from ..util.optimizer_util import restore_training_state
 from .BaseFluxSetup import BaseFluxSetup
 from ..util.config.plain import plain
@@ -59,16 +59,7 @@ class FluxLoRASetup(BaseFluxSetup):
         model.transformer.lora = model.transformer_lora
         params = self.create_parameters(model, config)
         model.parameters = params
-        oc = config.optimizer
-        if oc.optimizer != "ADAMW":
-            raise NotImplementedError(f"optimizer {oc.optimizer}: only ADAMW is on the hot path")
-        model.optimizer = FusedAdamW(model.transformer_lora.store, params.parameters_for_optimizer(config),
-                                     lr=config.learning_rate,
-                                     betas=(oc.beta1 if oc.beta1 is not None else 0.9,
-                                            oc.beta2 if oc.beta2 is not None else 0.999),
-                                     eps=oc.eps if oc.eps is not None else 1e-8,
-                                     weight_decay=oc.weight_decay if oc.weight_decay is not None else 1e-2,
-                                     stochastic_rounding=oc.stochastic_rounding)
+        model.optimizer = create_optimizer(model.transformer_lora.store, params.parameters_for_optimizer(config), config)
         model.param_group_mapping = params.unique_name_mapping()
         restore_training_state(model, config)
 

@@ -1,12 +1,12 @@
 """Full fine-tune plugin (mirrors modules/modelSetup/StableDiffusionXLFineTuneSetup.py:26-164):
-parameter groups, optimizer creation (create.py:509-534 -> FusedAdamW), device placement."""
+parameter groups, optimizer creation (util/create.py create_optimizer: fused AdamW or Adafactor), device placement."""
 from __future__ import annotations
 
 import torch
 
 from ..util.dtype_util import dtype_plan
 from ..util.NamedParameterGroup import NamedParameterGroup, NamedParameterGroupCollection
-from ..util.optimizer.adamw_fused import FusedAdamW
+from ..util.create import create_optimizer
 from ..util.optimizer_util import restore_training_state
 from .BaseStableDiffusionXLSetup import BaseStableDiffusionXLSetup
 from ..util.config.plain import plain
@@ -34,16 +34,7 @@ class StableDiffusionXLFineTuneSetup(BaseStableDiffusionXLSetup):
         self.setup_optimizations(model, config)
         params = self.create_parameters(model, config)
         model.parameters = params
-        oc = config.optimizer
-        if oc.optimizer != "ADAMW":
-            raise NotImplementedError(f"optimizer {oc.optimizer}: only ADAMW is on the hot path")
-        model.optimizer = FusedAdamW(model.unet.store, params.parameters_for_optimizer(config),
-                                     lr=config.learning_rate,
-                                     betas=(oc.beta1 if oc.beta1 is not None else 0.9,
-                                            oc.beta2 if oc.beta2 is not None else 0.999),
-                                     eps=oc.eps if oc.eps is not None else 1e-8,
-                                     weight_decay=oc.weight_decay if oc.weight_decay is not None else 1e-2,
-                                     stochastic_rounding=oc.stochastic_rounding)
+        model.optimizer = create_optimizer(model.unet.store, params.parameters_for_optimizer(config), config)
         model.param_group_mapping = params.unique_name_mapping()
         restore_training_state(model, config)
 

@@ -103,15 +103,15 @@ class GenericTrainer(TimedActionMixin):
         self._attach_norm_overlap()
 
     def _attach_norm_overlap(self):
-        """eager steps, clip on, the fused AdamW: clip_grad_norm_'s norm pass runs during backward
+        """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor): clip_grad_norm_'s norm pass runs during backward
         (util/optimizer/adamw_fused.OverlappedGradNorm) -- in one process as gradient ranges finish, under data
         parallel as the reducer's buckets finish their all-reduce (the norm of the global-mean gradients)."""
         import os
 
         from ..module import streams as S
-        from ..util.optimizer.adamw_fused import FusedAdamW, OverlappedGradNorm
+        from ..util.optimizer.adamw_fused import FlatStoreOptimizer, OverlappedGradNorm
         opt = getattr(self.model, "optimizer", None)
-        if (isinstance(opt, FusedAdamW) and self.graphs is None and self.config.clip_grad_norm
+        if (isinstance(opt, FlatStoreOptimizer) and self.graphs is None and self.config.clip_grad_norm
                 and opt.store.grad.is_cuda and S.enabled() and os.environ.get("OTAMD_NORM_OVERLAP", "1") != "0"
                 and opt.norm_overlap is None):
             opt.norm_overlap = OverlappedGradNorm(opt, reducer=self.reducer,

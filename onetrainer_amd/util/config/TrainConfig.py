@@ -19,6 +19,13 @@ class OptimizerConfig:
     beta2: float | None = None
     eps: float | None = None
     weight_decay: float | None = None
+    # ADAFACTOR (TrainConfig.py optimizer part; None resolves as modules/util/create.py:922-934 does)
+    eps2: float | None = None
+    clip_threshold: float | None = None
+    decay_rate: float | None = None
+    scale_parameter: bool | None = None
+    relative_step: bool | None = None
+    warmup_init: bool | None = None
     stochastic_rounding: bool = True
     fused_back_pass: bool = False
     foreach: bool | None = False

@@ -1,5 +1,5 @@
 """Factories (mirrors the parts of modules/util/create.py the hot path uses:
-create_model_setup 285-353, create_optimizer 509-534 via setup_model, create_lr_scheduler
+create_model_setup 285-353, create_optimizer 509-534 (ADAMW) and 914-936 (ADAFACTOR), create_lr_scheduler
 1114-1232, create_noise_scheduler 1235-1373)."""
 from __future__ import annotations
 
@@ -99,3 +99,44 @@ def create_model_setup(config, train_device, dp_rank=0, dp_world=1):
             from ..modelSetup.StableDiffusionXLLoRASetup import StableDiffusionXLLoRASetup as S
         return S(train_device, dp_rank=dp_rank, dp_world=dp_world)
     raise NotImplementedError(f"training method {config.training_method}")
+
+
+def adafactor_options(oc) -> dict:
+    """OptimizerConfig -> transformers.Adafactor arguments, None resolved exactly as create.py:922-934 resolves it
+    (scale_parameter and relative_step fall back to True there; the UI defaults, optimizer_util.py:70-82, set both
+    False explicitly, and an explicit value wins)."""
+    def pick(name, default):
+        v = getattr(oc, name, None)
+        return v if v is not None else default
+    return dict(eps=pick("eps", 1e-30), eps2=pick("eps2", 1e-3), clip_threshold=pick("clip_threshold", 1.0),
+                decay_rate=pick("decay_rate", -0.8), beta1=getattr(oc, "beta1", None),
+                weight_decay=pick("weight_decay", 0.0), scale_parameter=pick("scale_parameter", True),
+                relative_step=pick("relative_step", True), warmup_init=pick("warmup_init", False))
+
+
+def create_optimizer(store, groups, config):
+    """the fused optimizer over `store` for config.optimizer (create.py:509-534 ADAMW + patch_adamw, 914-936
+    ADAFACTOR + patch_adafactor).  Anything else is refused: there is no eager fall-back."""
+    config = plain(config)
+    oc = config.optimizer
+    name = str(oc.optimizer)
+    if name == "ADAMW":
+        from .optimizer.adamw_fused import FusedAdamW
+        return FusedAdamW(store, groups, lr=config.learning_rate,
+                          betas=(oc.beta1 if oc.beta1 is not None else 0.9,
+                                 oc.beta2 if oc.beta2 is not None else 0.999),
+                          eps=oc.eps if oc.eps is not None else 1e-8,
+                          weight_decay=oc.weight_decay if oc.weight_decay is not None else 1e-2,
+                          stochastic_rounding=oc.stochastic_rounding)
+    if name == "ADAFACTOR":
+        from .optimizer.adafactor_fused import FusedAdafactor
+        o = adafactor_options(oc)
+        if str(getattr(config, "learning_rate_scheduler", "CONSTANT")) == "ADAFACTOR":
+            raise NotImplementedError("learning_rate_scheduler ADAFACTOR (relative_step) is not on the hot path: "
+                                      "set relative_step=False and a learning rate")
+        return FusedAdafactor(store, groups, lr=config.learning_rate, eps=(o["eps"], o["eps2"]),
+                              clip_threshold=o["clip_threshold"], decay_rate=o["decay_rate"], beta1=o["beta1"],
+                              weight_decay=o["weight_decay"], scale_parameter=o["scale_parameter"],
+                              relative_step=o["relative_step"], warmup_init=o["warmup_init"],
+                              stochastic_rounding=bool(oc.stochastic_rounding))
+    raise NotImplementedError(f"optimizer {name}: only ADAMW and ADAFACTOR are on the hot path")

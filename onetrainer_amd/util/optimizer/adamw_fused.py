@@ -31,20 +31,17 @@ from ... import _lib
 from ... import kernels as K
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, store, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 stochastic_rounding=True, seed=0):
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        foreach=False, capturable=False, differentiable=False, fused=False)
-        super().__init__(param_groups, defaults)
+class FlatStoreOptimizer(torch.optim.Optimizer):
+    """What every fused optimizer over a FlatParamStore shares: the parameter groups as contiguous element ranges,
+    the per-tensor chunk table of the global grad norm, clip_grad_norm_ (whose coefficient stays on the device and is
+    applied inside the next step()) and the hook OverlappedGradNorm attaches to.  FusedAdamW and FusedAdafactor
+    (adafactor_fused.py) derive from it."""
+
+    def _init_store(self, store):
         self.store = store
-        self.stochastic_rounding = stochastic_rounding
-        self.seed = seed
         # fp32 master weights (module/param_store.py `master`): fp32 moments, the reference's fp32 AdamW path
         # (adamw_extensions.py:125-148 without stochastic rounding, which applies to bf16 parameters only)
         self.master = getattr(store, "master", None)
-        self.exp_avg = torch.zeros_like(self.master if self.master is not None else store.data)
-        self.exp_avg_sq = torch.zeros_like(self.exp_avg)
         self._norm_dtype = K.grad_norm_dtype(store.grad, self.master is not None) if store.grad is not None else 0
         self._ptr2name = {store.params[n].data_ptr(): n for n in store.order}
         self._ranges = []
@@ -54,13 +51,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 s = store.slots[self._ptr2name[p.data_ptr()]]
                 offs.append((s.offset, s.offset + s.numel))
             b, e = min(o[0] for o in offs), max(o[1] for o in offs)
-            covered = sum(o[1] - o[0] for o in offs)
             span = [s for s in store.order if b <= store.slots[s].offset < e]
             if len(span) != len(offs):
                 raise ValueError("each optimizer param group must be a contiguous range of the flat store")
             self._ranges.append((b, e))
-            del covered
-        self.steps = [0 for _ in self.param_groups]
         # per-tensor chunk table for the global grad norm
         chunks = []
         for ti, n in enumerate(store.order):
@@ -78,26 +72,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.clip_out = torch.zeros(2, dtype=torch.float32, device=store.device)   # [coef, total norm]
         self._chunk_tensor = [c[2] for c in chunks]
         self.norm_overlap = None   # OverlappedGradNorm, attached by the trainer (single process, clip on)
-        # overlapped update: chunk boundaries on tensor boundaries, ~numel / 16 each
-        self.overlap = (store.device.type == "cuda" and store.dtype == torch.bfloat16 and store.numel >= (1 << 26)
-                        and self.master is None and os.environ.get("OTAMD_OPT_OVERLAP", "0") == "1")
-        self._opt_chunks = []
-        if self.overlap:
-            # chunk ends at 1/256, 1/128, ..., 1/16 of the store, then every 1/16 (tensor boundaries): the forward's first
-            # layers wait only for a small first chunk, the rest of the update runs beside them
-            ends = [store.numel >> k for k in range(8, 4, -1)] + [store.numel * i // 16 for i in range(1, 17)]
-            b, t = 0, 0
-            for n in store.order:
-                s = store.slots[n]
-                e = (s.offset + s.numel + 7) // 8 * 8
-                if t < len(ends) and e >= ends[t]:
-                    self._opt_chunks.append((b, e))
-                    b = e
-                    while t < len(ends) and ends[t] <= e:
-                        t += 1
-            if b < store.numel:
-                self._opt_chunks.append((b, store.numel))
-            self._stream = torch.cuda.Stream(device=store.device)
+        self._pending_clip = False
 
     # --- clip_grad_norm_ (GenericTrainer.py:712-713) ----------------------------------------------
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
@@ -125,6 +100,44 @@ class FusedAdamW(torch.optim.Optimizer):
                              max_norm, self.clip_out, fp32_semantics=self.master is not None)
         self._pending_clip = True
         return self.clip_out[1]
+
+    def zero_grad(self, set_to_none: bool = True):
+        """grads are views of the flat store that the next backward overwrites; nothing to clear."""
+        self.store.accumulating = False
+
+
+class FusedAdamW(FlatStoreOptimizer):
+    def __init__(self, store, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 stochastic_rounding=True, seed=0):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=False, capturable=False, differentiable=False, fused=False)
+        super().__init__(param_groups, defaults)
+        self._init_store(store)
+        self.stochastic_rounding = stochastic_rounding
+        self.seed = seed
+        self.exp_avg = torch.zeros_like(self.master if self.master is not None else store.data)
+        self.exp_avg_sq = torch.zeros_like(self.exp_avg)
+        self.steps = [0 for _ in self.param_groups]
+        # overlapped update: chunk boundaries on tensor boundaries, ~numel / 16 each
+        self.overlap = (store.device.type == "cuda" and store.dtype == torch.bfloat16 and store.numel >= (1 << 26)
+                        and self.master is None and os.environ.get("OTAMD_OPT_OVERLAP", "0") == "1")
+        self._opt_chunks = []
+        if self.overlap:
+            # chunk ends at 1/256, 1/128, ..., 1/16 of the store, then every 1/16 (tensor boundaries): the forward's first
+            # layers wait only for a small first chunk, the rest of the update runs beside them
+            ends = [store.numel >> k for k in range(8, 4, -1)] + [store.numel * i // 16 for i in range(1, 17)]
+            b, t = 0, 0
+            for n in store.order:
+                s = store.slots[n]
+                e = (s.offset + s.numel + 7) // 8 * 8
+                if t < len(ends) and e >= ends[t]:
+                    self._opt_chunks.append((b, e))
+                    b = e
+                    while t < len(ends) and ends[t] <= e:
+                        t += 1
+            if b < store.numel:
+                self._opt_chunks.append((b, store.numel))
+            self._stream = torch.cuda.Stream(device=store.device)
 
     def _groups_struct(self, idx_list, steps=None):
         arr = []
@@ -206,10 +219,6 @@ class FusedAdamW(torch.optim.Optimizer):
         K.adamw_bf16(st.data, st.grad, self.exp_avg, self.exp_avg_sq, groups, clip_coef=None,
                      stochastic_rounding=self.stochastic_rounding, seed=self.seed, begin=b, end=e)
 
-    def zero_grad(self, set_to_none: bool = True):
-        """grads are views of the flat store that the next backward overwrites; nothing to clear."""
-        self.store.accumulating = False
-
     # --- torch AdamW-compatible state -------------------------------------------------------------
     def state_dict(self):
         self.store.wait_params()
@@ -269,7 +278,7 @@ class OverlappedGradNorm:
     its collective completes (trainer/ddp.py reduced_hooks); only the last bucket's sums follow the backward.
     OTAMD_NORM_OVERLAP=0 disables it."""
 
-    def __init__(self, opt: FusedAdamW, bucket_bytes: int = 64 << 20, reducer=None):
+    def __init__(self, opt: FlatStoreOptimizer, bucket_bytes: int = 64 << 20, reducer=None):
         self.opt = opt
         self.dp = reducer is not None
         store = opt.store

@@ -1,0 +1,215 @@
+"""Fused Adafactor (csrc/adafactor.hip, util/optimizer/adafactor_fused.py) on the GPU against the NumPy restatement
+tests/_oracle_adafactor.py, which tests/test_adafactor_oracle.py pins to the reference's own run.  The bounds are the
+ones derived there: states within ((n - 1) + 8 k) 2^-24 relative, fp32 parameters within the accumulated
+dmag factor_eps 2^-24 + 4 2^-24 |p|, bf16 parameters equal or one bf16 ulp apart with at most 1e-3 of them apart."""
+import numpy as np
+import pytest
+import torch
+
+import _oracle_adafactor as AF
+from onetrainer_amd.module.param_store import FlatParamStore
+from onetrainer_amd.util.optimizer.adafactor_fused import FusedAdafactor
+from oracle import adamw as OA
+
+pytestmark = pytest.mark.gpu
+
+CFG = dict(scale_parameter=True, weight_decay=0.01, clip_threshold=1.0)
+LRS = (3e-2, 1e-2)          # two parameter groups
+SPLIT = 5                   # SHAPES[:SPLIT] -> group 0, the rest -> group 1
+STATE_KEYS = {"row": "exp_avg_sq_row", "col": "exp_avg_sq_col", "full": "exp_avg_sq"}
+
+
+def bits(t):
+    return t.detach().cpu().contiguous().view(torch.int16).numpy().astype(np.uint16)
+
+
+def make(dev, form, sr=False, seed=11, cfg=CFG):
+    master = form == "master"
+    dtype = torch.float32 if form == "f32" else torch.bfloat16
+    st = FlatParamStore([(n, s, "a" if i < SPLIT else "b") for i, (n, s) in enumerate(AF.SHAPES)], dtype, dev,
+                        master=master)
+    for n, s in AF.SHAPES:
+        st.write(n, torch.from_numpy(AF.param0(n, s)))
+    groups = [{"params": [st.params[n] for n, _ in AF.SHAPES[:SPLIT]], "lr": LRS[0]},
+              {"params": [st.params[n] for n, _ in AF.SHAPES[SPLIT:]], "lr": LRS[1]}]
+    opt = FusedAdafactor(st, groups, lr=LRS[0], relative_step=False, stochastic_rounding=sr, seed=seed, **cfg)
+    return st, opt
+
+
+def set_grads(st, k, mult=1.0):
+    for n, s in AF.SHAPES:
+        st.params[n].grad.copy_(torch.from_numpy(AF.grad(n, s, k) * np.float32(mult)))
+    # "zero" received no gradient: the store zeroes it (finish_backward), the step sees zeros
+
+
+def value(st, n):
+    return st.value(n).detach().float().cpu().numpy()
+
+
+def states(opt, n):
+    v = opt._views(n)
+    return {k: v[STATE_KEYS[k]].cpu().numpy() for k in STATE_KEYS if STATE_KEYS[k] in v}
+
+
+@pytest.mark.parametrize("clip", [False, True])
+@pytest.mark.parametrize("form", ["f32", "master", "bf16", "bf16_sr"])
+def test_three_steps_against_the_oracle(dev, form, clip):
+    sr = form == "bf16_sr"
+    is_bf16 = form.startswith("bf16")
+    st, opt = make(dev, form, sr=sr)
+    ost = {n: AF.new_state(s) for n, s in AF.SHAPES}
+    apart = total = 0
+    for k in range(AF.STEPS):
+        set_grads(st, k, 3.0 if clip else 1.0)
+        coef = None
+        if clip:
+            opt.clip_grad_norm_(1.0)
+            gl = [st.params[n].grad for n, _ in AF.SHAPES]
+            if form == "f32":
+                _, coef = OA.clip_grad_norm_f32([g.cpu().numpy().reshape(-1) for g in gl], 1.0)
+            elif form == "master":
+                _, coef = OA.clip_grad_norm_f32([OA.bf16_to_f32(bits(g).reshape(-1)) for g in gl], 1.0)
+            else:
+                _, _, coef = OA.clip_grad_norm_bf16([bits(g).reshape(-1) for g in gl], 1.0)
+            got_coef = opt.clip_out[0].item()
+            if is_bf16:
+                assert got_coef == coef and coef < 1.0
+            else:   # fp32 norms: the kernel folds the ten tensors' norms in fp32, the oracle in float64 -> 16 U;
+                assert abs(got_coef - coef) <= 16 * AF.U * coef and coef < 1.0   # the step under test gets the
+                coef = np.float32(got_coef)                                      # coefficient the device holds
+        before = {n: value(st, n) for n, _ in AF.SHAPES}
+        seed = (opt.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        opt.step()
+        if is_bf16:
+            assert opt.seed == seed
+        for i, (n, s) in enumerate(AF.SHAPES):
+            g = st.params[n].grad.float().cpu().numpy()
+            if coef is not None:
+                g = OA.rbf(g * np.float32(coef)) if is_bf16 else g * np.float32(coef)
+            x, info = AF.adafactor_step(before[n], g, ost[n], k + 1, lr=LRS[0] if i < SPLIT else LRS[1], **CFG)
+            for key, arr in states(opt, n).items():
+                ref = ost[n][key]
+                red = {"row": s[-1], "col": s[-2] if len(s) >= 2 else 1, "full": 1}[key]
+                assert np.all(np.abs(arr.astype(np.float64) - ref) <= AF.state_eps(red, k + 1) * np.abs(ref)), (n, k, key)
+            got = value(st, n)
+            if is_bf16:
+                slot = st.slots[n]
+                if sr:
+                    rand = OA.sr_bits(seed, np.arange(slot.offset, slot.offset + slot.numel))
+                    want = OA.copy_stochastic(x.reshape(-1), rand)
+                else:
+                    want = OA.f32_to_bf16_bits(x).reshape(-1)
+                d = AF.bf16_ulps(bits(st.params[n]).reshape(-1), want)
+                assert d.max() <= 1, (n, k, int(d.max()))
+                apart += int((d != 0).sum())
+                total += d.size
+            else:
+                # every step restarts from the GPU's parameters, so the bound is one step's (the states carry on)
+                bound = info["dmag"] * AF.factor_eps(s, CFG["scale_parameter"]) * AF.U + 4 * AF.U * np.abs(x)
+                assert np.all(np.abs(got.astype(np.float64) - x) <= bound), (n, k)
+                if form == "master":   # the working copy is rne(master), bit for bit
+                    assert np.array_equal(bits(st.params[n]), OA.f32_to_bf16_bits(got))
+    if is_bf16:
+        assert apart <= 1e-3 * total, (apart, total)
+
+
+def _run(dev, form, sr, steps=AF.STEPS, clip=True):
+    st, opt = make(dev, form, sr=sr)
+    for k in range(steps):
+        set_grads(st, k, 3.0)
+        if clip:
+            opt.clip_grad_norm_(1.0)
+        opt.step()
+    torch.cuda.synchronize()
+    return st, opt
+
+
+@pytest.mark.parametrize("form, sr", [("bf16", True), ("master", False)])
+def test_second_run_gives_identical_bits(dev, form, sr):
+    a, oa = _run(dev, form, sr)
+    b, ob = _run(dev, form, sr)
+    assert torch.equal(a.data.view(torch.int16), b.data.view(torch.int16))
+    assert torch.equal(oa.state_buf.view(torch.int32), ob.state_buf.view(torch.int32))
+    if form == "master":
+        assert torch.equal(a.master.view(torch.int32), b.master.view(torch.int32))
+
+
+@pytest.mark.parametrize("name", ["m300x1030", "conv3", "v37", "m2x4100"])
+def test_step_parameter_is_the_tensors_slice_of_a_store_step(dev, name):
+    whole, _ = _run(dev, "bf16", False, steps=1, clip=False)
+    st, opt = make(dev, "bf16")
+    set_grads(st, 0, 3.0)
+    before = st.data.clone()
+    gi = 0 if [n for n, _ in AF.SHAPES].index(name) < SPLIT else 1
+    opt.step_parameter(st.params[name], opt.param_groups[gi], 0)
+    torch.cuda.synchronize()
+    s = st.slots[name]
+    sl = slice(s.offset, s.offset + s.numel)
+    assert torch.equal(st.data[sl].view(torch.int16), whole.data[sl].view(torch.int16))
+    assert not torch.equal(st.data[sl], before[sl])
+    keep = torch.ones(st.numel, dtype=torch.bool, device=st.data.device)
+    keep[sl] = False
+    assert torch.equal(st.data[keep].view(torch.int16), before[keep].view(torch.int16))   # neighbours untouched
+
+
+@pytest.mark.parametrize("form, sr", [("bf16", True), ("f32", False)])
+def test_state_dict_resumes_bit_exactly(dev, form, sr):
+    a, oa = _run(dev, form, sr, steps=2)
+    sd = oa.state_dict()
+    assert set(sd) == {"state", "param_groups", "sr_seed"}
+    first = sd["state"][0]
+    assert set(first) == {"step", "RMS", "exp_avg_sq_row", "exp_avg_sq_col"} and first["step"] == 2
+    assert first["exp_avg_sq_row"].shape == (64,) and first["exp_avg_sq_col"].shape == (70,)
+    assert set(sd["state"][6]) == {"step", "RMS", "exp_avg_sq"}
+    assert tuple(sd["state"][4]["exp_avg_sq_row"].shape) == (3, 5, 3)
+    b, ob = make(dev, form, sr=sr, seed=999)
+    b.data.copy_(a.data)
+    ob.load_state_dict(sd)
+    for st, opt in ((a, oa), (b, ob)):
+        set_grads(st, 2, 3.0)
+        opt.clip_grad_norm_(1.0)
+        opt.step()
+    torch.cuda.synchronize()
+    assert torch.equal(a.data.view(torch.uint8), b.data.view(torch.uint8))
+    assert torch.equal(oa.state_buf.view(torch.int32), ob.state_buf.view(torch.int32))
+
+
+def _trainer_run(dev, method, overlap=True, steps=3):
+    from onetrainer_amd.dataLoader.SyntheticDataLoader import synthetic_sdxl_batch
+    from onetrainer_amd.module import unet as U
+    from onetrainer_amd.trainer.GenericTrainer import GenericTrainer
+    from onetrainer_amd.util import create
+    from onetrainer_amd.util.config.TrainConfig import TrainConfig
+    cfg = TrainConfig.default_values()
+    cfg.batch_size = 2
+    cfg.learning_rate_warmup_steps = 0
+    cfg.clip_grad_norm = 0.05
+    cfg.training_method = method
+    if method == "LORA":
+        cfg.lora_rank, cfg.lora_alpha = 8, 8.0
+    cfg.optimizer.optimizer = "ADAFACTOR"      # the UI defaults (optimizer_util.py:70-82)
+    cfg.optimizer.scale_parameter = False
+    cfg.optimizer.relative_step = False
+    cfg.optimizer.warmup_init = False
+    model = create.create_model(cfg, dev, seed=7, unet_config=U.tiny_sdxl_config())
+    tr = GenericTrainer(cfg, model=model)
+    tr.start()
+    opt = model.optimizer
+    assert isinstance(opt, FusedAdafactor)
+    assert opt.norm_overlap is not None
+    if not overlap:
+        opt.norm_overlap = None
+    batch = synthetic_sdxl_batch(2, 128, 128, dev, seed=3, te1_dim=48, te2_dim=48, pooled_dim=64)
+    losses = [float(tr.train_step(batch)) for _ in range(steps)]
+    torch.cuda.synchronize()
+    return losses, model.train_store.data.clone()
+
+
+@pytest.mark.parametrize("method", ["FINE_TUNE", "LORA"])
+def test_trainer_steps_with_adafactor(dev, method):
+    l1, p1 = _trainer_run(dev, method)
+    l2, p2 = _trainer_run(dev, method)
+    l3, p3 = _trainer_run(dev, method, overlap=False)
+    assert all(np.isfinite(l1)) and len(l1) == 3
+    assert l1 == l2 and torch.equal(p1.view(torch.uint8), p2.view(torch.uint8))      # bitwise repeatable
+    assert torch.equal(p1.view(torch.uint8), p3.view(torch.uint8))                   # overlapped norm = end-of-step norm
