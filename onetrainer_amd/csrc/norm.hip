@@ -788,7 +788,11 @@ __global__ void __launch_bounds__(512) ln_param_part_kernel(const bf16_t* __rest
   }
 }
 
-// chunks per lane for a row of C8 16-byte chunks: L = C8 / CPL a power of two <= 64 (0: no fit)
+// chunks per lane for a row of C8 16-byte chunks: L = C8 / CPL a power of two <= 64 (0: no fit).
+// Under the launchers' C <= 64 * 8 * LN_MAXCH = 2048 (C8 <= 256) candidates 6 and 8 are never returned: 3 and 4
+// come first and take every C8 = 6 L' / 8 L' with L' <= 32, and L' = 64 is C = 3072 / 4096.  The CPL 6 and 8
+// instantiations below are therefore unreachable today (tests/_norm_edges.py mirrors this function and
+// tests/test_norm_edges_ref.py asserts the reachable set).
 static int ln_pick(int C8, int* L) {
   const int cands[] = {5, 4, 3, 6, 2, 8, 1};
   for (int c : cands) {
