@@ -18,6 +18,7 @@
 // MN-contiguous tiles with ds_read_b64_tr_b16 (hardware transpose), both XOR-swizzled
 // to be bank-conflict free.  The MFMA is issued with swapped operands (B-fragment as
 // the MFMA A operand) so each lane ends with 4 consecutive output columns.
+#include "defer.h"
 #include "gemm.h"
 #include "gemm_tiles.h"
 
@@ -284,6 +285,20 @@ __global__ void __launch_bounds__(NTHREADS, 2) gemm_kernel(GemmArgs args) {
 // Sum the split-K fp32 slabs and apply the epilogue.  V consecutive columns per thread (8 when
 // N % 8 == 0: one 16-byte bf16 store), every split's loads issued before the adds (the slabs were
 // just written and mostly sit in the MALL: latency, not bandwidth, bounds a dependent chain).
+// element m of the fused column sums: the per-split partials summed in split order, stored or accumulated
+__device__ __forceinline__ void colsum_fold(const float* slab, int M, int splits, unsigned m, void* colsum, int f32,
+                                            int acc) {
+  float t = slab[m];
+  for (int z = 1; z < splits; ++z) t += slab[(long long)z * M + m];
+  if (f32) {
+    float* d = reinterpret_cast<float*>(colsum) + m;
+    *d = acc ? *d + t : t;
+  } else {
+    bf16_t* d = reinterpret_cast<bf16_t*>(colsum) + m;
+    *d = f2bf(acc ? bf2f(*d) + t : t);
+  }
+}
+
 template <int V>
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(GemmArgs args, int splits) {
   const unsigned NV = (unsigned)args.N / V;
@@ -292,18 +307,9 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(GemmArgs args, int s
     const unsigned m = i / NV, n = (i - m * NV) * V;
     splitk_combine<V>(args, m, n, splits);
   }
-  if (args.colsum) {   // the fused column sums' per-split partials, summed in split order
-    for (unsigned m = blockIdx.x * 256u + threadIdx.x; m < (unsigned)args.M; m += gridDim.x * 256u) {
-      float t = args.colsum_slab[m];
-      for (int z = 1; z < splits; ++z) t += args.colsum_slab[(long long)z * args.M + m];
-      if (args.colsum_f32) {
-        float* d = reinterpret_cast<float*>(args.colsum) + m;
-        *d = args.colsum_acc ? *d + t : t;
-      } else {
-        bf16_t* d = reinterpret_cast<bf16_t*>(args.colsum) + m;
-        *d = f2bf(args.colsum_acc ? bf2f(*d) + t : t);
-      }
-    }
+  if (args.colsum) {
+    for (unsigned m = blockIdx.x * 256u + threadIdx.x; m < (unsigned)args.M; m += gridDim.x * 256u)
+      colsum_fold(args.colsum_slab, args.M, splits, m, args.colsum, args.colsum_f32, args.colsum_acc);
   }
 }
 
@@ -340,67 +346,45 @@ __global__ void __launch_bounds__(256) splitk_reduce_grouped_kernel(SplitkBatch 
     splitk_combine<4>(a, m, n, d.splits);
   }
   if (d.colsum) {
-    for (unsigned m = lb * 256u + threadIdx.x; m < (unsigned)d.M; m += nb * 256u) {
-      float t = d.colsum_slab[m];
-      for (int z = 1; z < d.splits; ++z) t += d.colsum_slab[(long long)z * d.M + m];
-      if (d.flags & 4) {
-        float* p = reinterpret_cast<float*>(d.colsum) + m;
-        *p = (d.flags & 8) ? *p + t : t;
-      } else {
-        bf16_t* p = reinterpret_cast<bf16_t*>(d.colsum) + m;
-        *p = f2bf((d.flags & 8) ? bf2f(*p) + t : t);
-      }
-    }
+    for (unsigned m = lb * 256u + threadIdx.x; m < (unsigned)d.M; m += nb * 256u)
+      colsum_fold(d.colsum_slab, d.M, d.splits, m, d.colsum, d.flags & 4, d.flags & 8);
   }
 }
 
-struct DeferState {
-  char* arena = nullptr;
-  long long bytes = 0, used = 0;
-  uintptr_t out_lo = 0, out_hi = 0;   // only outputs inside this range are deferred
-  SplitkBatch batch{};
-  uintptr_t lo[kMaxDefer], hi[kMaxDefer];   // byte ranges each pending reduce writes (C, and the colsum)
-  uintptr_t clo[kMaxDefer], chi[kMaxDefer];
-};
-static std::mutex g_defer_mu;
-static std::unordered_map<hipStream_t, DeferState> g_defer;
-static long long g_defer_gemms = 0, g_defer_launches = 0;   // otamd_gemm_defer_stats
-
-static int defer_flush_locked(DeferState& st, hipStream_t stream) {
-  if (st.batch.n > 0) {
-    splitk_reduce_grouped_kernel<<<st.batch.blocks, 256, 0, stream>>>(st.batch);
-    g_defer_gemms += st.batch.n;
-    ++g_defer_launches;
-    st.batch.n = 0;
-    st.batch.blocks = 0;
-    OTAMD_CHECK_LAUNCH();
-  }
-  st.used = 0;
+// the grouped launch DeferQueue flushes with
+static int launch_splitk_grouped(const SplitkBatch& bt, hipStream_t stream) {
+  splitk_reduce_grouped_kernel<<<bt.blocks, 256, 0, stream>>>(bt);
+  OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }
+static_assert(kDeferOk == OTAMD_OK && kDeferInvalid == OTAMD_EINVAL, "defer.h restates the status codes");
+static DeferQueue<SplitkBatch, hipStream_t> g_defer;
+struct ByteRange { uintptr_t lo, hi; };
+static std::unordered_map<hipStream_t, ByteRange> g_defer_out;   // only outputs inside are deferred (under g_defer.mu)
 
-static void c_range(const GemmArgs& a, uintptr_t& lo, uintptr_t& hi) {
-  const int es = a.c_f32 ? 4 : 2;
-  lo = (uintptr_t)a.C;
-  hi = lo + ((long long)(a.M - 1) * a.ldc + a.N) * es;
+static bool overlaps(ByteRange a, ByteRange b) { return a.lo < b.hi && b.lo < a.hi; }
+// the bytes a GEMM's reduce writes: C, and the fused column sums (empty without them)
+static ByteRange c_range(const void* C, long long ldc, int M, int N, bool f32) {
+  return {(uintptr_t)C, (uintptr_t)C + ((long long)(M - 1) * ldc + N) * (f32 ? 4 : 2)};
+}
+static ByteRange colsum_range(const void* colsum, int M, bool f32) {
+  return {(uintptr_t)colsum, (uintptr_t)colsum + (colsum ? (uintptr_t)M * (f32 ? 4 : 2) : 0)};
 }
 
 // a GEMM on a deferring stream: a pending reduce whose output this GEMM reads or writes is flushed first
 static int defer_guard(const GemmArgs& a, hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  auto it = g_defer.find(stream);
-  if (it == g_defer.end() || it->second.batch.n == 0) return OTAMD_OK;
-  DeferState& st = it->second;
-  uintptr_t lo, hi;
-  c_range(a, lo, hi);
-  const uintptr_t cl = (uintptr_t)a.colsum, ch = cl + (a.colsum ? (uintptr_t)a.M * (a.colsum_f32 ? 4 : 2) : 0);
-  const uintptr_t in[3][2] = {{(uintptr_t)a.A, (uintptr_t)a.A + 1}, {(uintptr_t)a.B, (uintptr_t)a.B + 1}, {lo, hi}};
-  for (int i = 0; i < st.batch.n; ++i) {
-    bool hit = (lo < st.hi[i] && st.lo[i] < hi) || (a.colsum && cl < st.chi[i] && st.clo[i] < ch) ||
-               (a.colsum && cl < st.hi[i] && st.lo[i] < ch);
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  auto* st = g_defer.find(stream);
+  if (!st) return OTAMD_OK;
+  const ByteRange c = c_range(a.C, a.ldc, a.M, a.N, a.c_f32), cs = colsum_range(a.colsum, a.M, a.colsum_f32);
+  const ByteRange in[2] = {{(uintptr_t)a.A, (uintptr_t)a.A + 1}, {(uintptr_t)a.B, (uintptr_t)a.B + 1}};
+  for (int i = 0; i < st->batch.n; ++i) {
+    const SplitkDesc& d = st->batch.d[i];
+    const ByteRange pc = c_range(d.C, d.ldc, d.M, d.N, d.flags & 1), pcs = colsum_range(d.colsum, d.M, d.flags & 4);
+    bool hit = overlaps(c, pc) || (a.colsum && (overlaps(cs, pcs) || overlaps(cs, pc)));
     for (int j = 0; j < 2 && !hit; ++j)   // an operand that starts inside a pending output
-      hit = (in[j][0] < st.hi[i] && st.lo[i] < in[j][1]) || (in[j][0] < st.chi[i] && st.clo[i] < in[j][1]);
-    if (hit) return defer_flush_locked(st, stream);
+      hit = overlaps(in[j], pc) || overlaps(in[j], pcs);
+    if (hit) return g_defer.flush(stream, launch_splitk_grouped);
   }
   return OTAMD_OK;
 }
@@ -408,39 +392,24 @@ static int defer_guard(const GemmArgs& a, hipStream_t stream) {
 // slab memory for a deferrable split-K GEMM on a deferring stream (nullptr: not deferring / not eligible)
 static float* defer_slab(const GemmArgs& a, int splits, hipStream_t stream) {
   if (a.bias || a.rowvec || a.residual || a.batch > 1) return nullptr;
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  auto it = g_defer.find(stream);
-  if (it == g_defer.end()) return nullptr;
-  DeferState& st = it->second;
-  uintptr_t lo, hi;
-  c_range(a, lo, hi);
-  if (lo < st.out_lo || hi > st.out_hi) return nullptr;
-  if (a.colsum) {
-    const uintptr_t cl = (uintptr_t)a.colsum, ch = cl + (uintptr_t)a.M * (a.colsum_f32 ? 4 : 2);
-    if (cl < st.out_lo || ch > st.out_hi) return nullptr;
-  }
-  const long long need = (otamd_gemm_ws_bytes(&a, splits) + 255) / 256 * 256;
-  if (need > st.bytes) return nullptr;
-  if (st.batch.n == kMaxDefer || st.used + need > st.bytes) defer_flush_locked(st, stream);
-  float* p = reinterpret_cast<float*>(st.arena + st.used);
-  st.used += need;
-  return p;
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  auto out = g_defer_out.find(stream);
+  if (out == g_defer_out.end()) return nullptr;
+  const ByteRange c = c_range(a.C, a.ldc, a.M, a.N, a.c_f32), cs = colsum_range(a.colsum, a.M, a.colsum_f32);
+  if (c.lo < out->second.lo || c.hi > out->second.hi) return nullptr;
+  if (a.colsum && (cs.lo < out->second.lo || cs.hi > out->second.hi)) return nullptr;
+  return (float*)g_defer.slot(stream, otamd_gemm_ws_bytes(&a, splits), [](const SplitkBatch&) { return false; },
+                              launch_splitk_grouped);
 }
 
 static void defer_record(const GemmArgs& a, int splits, hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  DeferState& st = g_defer[stream];
-  SplitkDesc& d = st.batch.d[st.batch.n];
+  SplitkDesc d = {};
   d.slab = a.slab; d.C = a.C; d.ldc = a.ldc; d.M = a.M; d.N = a.N; d.splits = splits; d.alpha = a.alpha;
   d.flags = (a.c_f32 ? 1 : 0) | (a.accumulate ? 2 : 0) | (a.colsum_f32 ? 4 : 0) | (a.colsum_acc ? 8 : 0);
   d.colsum = a.colsum; d.colsum_slab = a.colsum_slab;
-  d.block0 = st.batch.blocks;
   const long long nv = (long long)a.M * a.N / 4;
-  st.batch.blocks += (unsigned)std::min<long long>((std::max<long long>(nv, a.M) + 255) / 256, 2048);
-  c_range(a, st.lo[st.batch.n], st.hi[st.batch.n]);
-  st.clo[st.batch.n] = (uintptr_t)a.colsum;
-  st.chi[st.batch.n] = (uintptr_t)a.colsum + (a.colsum ? (uintptr_t)a.M * (a.colsum_f32 ? 4 : 2) : 0);
-  ++st.batch.n;
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  g_defer.push(stream, d, (unsigned)std::min<long long>((std::max<long long>(nv, a.M) + 255) / 256, 2048));
 }
 
 // start deferring this stream's split-K reduces of outputs inside [out, out + out_bytes) into `arena` (>= 1 MiB,
@@ -448,45 +417,35 @@ static void defer_record(const GemmArgs& a, int splits, hipStream_t stream) {
 // flushed first
 OTAMD_API int otamd_gemm_defer_begin(hipStream_t stream, void* arena, long long bytes, const void* out,
                                      long long out_bytes) {
-  if (!arena || ((uintptr_t)arena & 255) || bytes < (1 << 20) || !out || out_bytes <= 0) return OTAMD_EINVAL;
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  DeferState& st = g_defer[stream];
-  defer_flush_locked(st, stream);
-  st.arena = (char*)arena;
-  st.bytes = bytes;
-  st.used = 0;
-  st.out_lo = (uintptr_t)out;
-  st.out_hi = (uintptr_t)out + (uintptr_t)out_bytes;
-  return OTAMD_OK;
+  if (!out || out_bytes <= 0) return OTAMD_EINVAL;
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  const int rc = g_defer.begin(stream, arena, bytes, launch_splitk_grouped);
+  if (rc != OTAMD_EINVAL) g_defer_out[stream] = {(uintptr_t)out, (uintptr_t)out + (uintptr_t)out_bytes};
+  return rc;
 }
 // launch the grouped reduce of every pending GEMM on this stream (stream-ordered); a no-op when none is pending
 OTAMD_API int otamd_gemm_defer_flush(hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  auto it = g_defer.find(stream);
-  return it == g_defer.end() ? OTAMD_OK : defer_flush_locked(it->second, stream);
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  return g_defer.flush(stream, launch_splitk_grouped);
 }
 // flush and leave defer mode
 OTAMD_API int otamd_gemm_defer_end(hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  auto it = g_defer.find(stream);
-  if (it == g_defer.end()) return OTAMD_OK;
-  const int rc = defer_flush_locked(it->second, stream);
-  g_defer.erase(it);
-  return rc;
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  g_defer_out.erase(stream);
+  return g_defer.end(stream, stream, launch_splitk_grouped);
 }
 // totals since load: out[0] = GEMMs whose reduce was deferred, out[1] = grouped reduce launches
 OTAMD_API int otamd_gemm_defer_stats(long long* out) {
   if (!out) return OTAMD_EINVAL;
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  out[0] = g_defer_gemms;
-  out[1] = g_defer_launches;
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  out[0] = g_defer.items;
+  out[1] = g_defer.launches;
   return OTAMD_OK;
 }
 // reduces pending on this stream
 OTAMD_API int otamd_gemm_defer_pending(hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  auto it = g_defer.find(stream);
-  return it == g_defer.end() ? 0 : it->second.batch.n;
+  std::lock_guard<std::mutex> lk(g_defer.mu);
+  return g_defer.pending(stream);
 }
 
 typedef void (*gemm_fn)(GemmArgs);

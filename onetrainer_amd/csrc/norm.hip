@@ -11,10 +11,11 @@
 // HBM-bound: fwd reads x twice (stats, apply) and writes y once; bwd reads x, dy twice and
 // writes dx once.
 #include "common.h"
+#include "defer.h"
 
 #include <stdlib.h>
+#include <initializer_list>
 #include <mutex>
-#include <unordered_map>
 
 __device__ __forceinline__ void store_param_grad(void* p, long long i, float v, int f32, int acc);
 
@@ -850,95 +851,61 @@ __global__ void __launch_bounds__(1024) ln_param_reduce_grouped_kernel(LnDeferBa
   ln_param_reduce_body(d.part, d.nb, d.C, d.dg, d.db, d.flags & 1, (d.flags >> 1) & 1, blockIdx.x - d.block0);
 }
 
-struct LnDeferState {
-  char* arena = nullptr;
-  long long bytes = 0, used = 0;
-  LnDeferBatch batch{};
-};
-static std::mutex g_ln_defer_mu;
-static std::unordered_map<hipStream_t, LnDeferState> g_ln_defer;
-static long long g_ln_defer_norms = 0, g_ln_defer_launches = 0;
-
-static void ln_defer_flush_locked(LnDeferState& st, hipStream_t stream) {
-  if (st.batch.n > 0) {
-    ln_param_reduce_grouped_kernel<<<st.batch.blocks, 1024, 0, stream>>>(st.batch);
-    g_ln_defer_norms += st.batch.n;
-    ++g_ln_defer_launches;
-    st.batch.n = 0;
-    st.batch.blocks = 0;
-  }
-  st.used = 0;
+// the grouped launch DeferQueue flushes with
+static int launch_ln_grouped(const LnDeferBatch& bt, hipStream_t stream) {
+  ln_param_reduce_grouped_kernel<<<bt.blocks, 1024, 0, stream>>>(bt);
+  OTAMD_CHECK_LAUNCH();
+  return OTAMD_OK;
 }
+static_assert(kDeferOk == OTAMD_OK && kDeferInvalid == OTAMD_EINVAL, "defer.h restates the status codes");
+static DeferQueue<LnDeferBatch, hipStream_t> g_ln_defer;
 
 // partial slab memory for one LayerNorm's parameter pass on a deferring stream (nullptr: not deferring, or the
 // partials do not fit the arena).  A pending reduce into the same dgamma / dbeta is flushed first (two grouped
 // reduces of one destination would race).
 static float* ln_defer_slot(long long need, const void* dg, const void* db, hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_ln_defer_mu);
-  auto it = g_ln_defer.find(stream);
-  if (it == g_ln_defer.end()) return nullptr;
-  LnDeferState& st = it->second;
-  need = (need + 255) / 256 * 256;
-  if (need > st.bytes) return nullptr;
-  bool clash = false;
-  for (int i = 0; i < st.batch.n && !clash; ++i) clash = st.batch.d[i].dg == dg || st.batch.d[i].db == db;
-  if (clash || st.batch.n == kLnMaxDefer || st.used + need > st.bytes) ln_defer_flush_locked(st, stream);
-  float* p = reinterpret_cast<float*>(st.arena + st.used);
-  st.used += need;
-  return p;
+  auto clash = [&](const LnDeferBatch& b) {
+    for (int i = 0; i < b.n; ++i)
+      if (b.d[i].dg == dg || b.d[i].db == db) return true;
+    return false;
+  };
+  std::lock_guard<std::mutex> lk(g_ln_defer.mu);
+  return (float*)g_ln_defer.slot(stream, need, clash, launch_ln_grouped);
 }
 
 static void ln_defer_record(const float* part, int nb, int C, void* dg, void* db, int f32, int acc,
                             hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_ln_defer_mu);
-  LnDeferState& st = g_ln_defer[stream];
-  LnDeferDesc& d = st.batch.d[st.batch.n++];
+  LnDeferDesc d = {};
   d.part = part; d.dg = dg; d.db = db; d.nb = nb; d.C = C; d.flags = (f32 ? 1 : 0) | (acc ? 2 : 0);
-  d.block0 = st.batch.blocks;
-  st.batch.blocks += (unsigned)((2 * C + 15) / 16);
+  std::lock_guard<std::mutex> lk(g_ln_defer.mu);
+  g_ln_defer.push(stream, d, (unsigned)((2 * C + 15) / 16));
 }
 
 // start deferring this stream's LayerNorm parameter reduces into `arena` (>= 1 MiB, 256-byte aligned, kept alive by
 // the caller until otamd_layernorm_defer_end); reduces pending from an earlier begin are flushed first
 OTAMD_API int otamd_layernorm_defer_begin(hipStream_t stream, void* arena, long long bytes) {
-  if (!arena || ((uintptr_t)arena & 255) || bytes < (1 << 20)) return OTAMD_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ln_defer_mu);
-  LnDeferState& st = g_ln_defer[stream];
-  ln_defer_flush_locked(st, stream);
-  st.arena = (char*)arena;
-  st.bytes = bytes;
-  st.used = 0;
-  OTAMD_CHECK_LAUNCH();
-  return OTAMD_OK;
+  std::lock_guard<std::mutex> lk(g_ln_defer.mu);
+  return g_ln_defer.begin(stream, arena, bytes, launch_ln_grouped);
 }
 // launch the grouped reduce of every pending LayerNorm on this stream (stream-ordered); a no-op when none is pending
 OTAMD_API int otamd_layernorm_defer_flush(hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(g_ln_defer_mu);
-  auto it = g_ln_defer.find(stream);
-  if (it != g_ln_defer.end()) ln_defer_flush_locked(it->second, stream);
-  OTAMD_CHECK_LAUNCH();
-  return OTAMD_OK;
+  std::lock_guard<std::mutex> lk(g_ln_defer.mu);
+  return g_ln_defer.flush(stream, launch_ln_grouped);
 }
 // flush and leave defer mode; the pending reduces go out on `launch` (the caller orders it after `stream`'s
 // parameter passes: the two-stream step flushes on the weight-gradient stream, whose join ends the backward)
 OTAMD_API int otamd_layernorm_defer_end_on(hipStream_t stream, hipStream_t launch) {
-  std::lock_guard<std::mutex> lk(g_ln_defer_mu);
-  auto it = g_ln_defer.find(stream);
-  if (it == g_ln_defer.end()) return OTAMD_OK;
-  ln_defer_flush_locked(it->second, launch);
-  g_ln_defer.erase(it);
-  OTAMD_CHECK_LAUNCH();
-  return OTAMD_OK;
+  std::lock_guard<std::mutex> lk(g_ln_defer.mu);
+  return g_ln_defer.end(stream, launch, launch_ln_grouped);
 }
 OTAMD_API int otamd_layernorm_defer_end(hipStream_t stream) { return otamd_layernorm_defer_end_on(stream, stream); }
 // out[0] = LayerNorms whose parameter reduce went out deferred, out[1] = grouped launches, out[2] = pending on stream
 OTAMD_API int otamd_layernorm_defer_stats(hipStream_t stream, long long* out) {
   if (!out) return OTAMD_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ln_defer_mu);
-  out[0] = g_ln_defer_norms;
-  out[1] = g_ln_defer_launches;
-  auto it = g_ln_defer.find(stream);
-  out[2] = it == g_ln_defer.end() ? 0 : it->second.batch.n;
+  std::lock_guard<std::mutex> lk(g_ln_defer.mu);
+  out[0] = g_ln_defer.items;
+  out[1] = g_ln_defer.launches;
+  out[2] = g_ln_defer.pending(stream);
   return OTAMD_OK;
 }
 
@@ -946,33 +913,62 @@ static int ln_param_grads(const void* x, long long ldx, const void* dy, long lon
                           const float* mean, const float* rstd, void* dgamma, void* dbeta, int param_f32,
                           int param_acc, float* part, hipStream_t stream);
 
-OTAMD_API int otamd_layernorm_fwd(const void* x, long long ldx, void* y, long long ldy, int rows, int C, float eps,
-                                  const void* gamma, const void* beta, float* mean, float* rstd, hipStream_t stream) {
-  if (!x || !y || !gamma || !beta || !mean || !rstd || rows < 0 || C % 8 || C > 64 * 8 * LN_MAXCH) return OTAMD_EINVAL;
-  if (ldx % 8 || ldy % 8 || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15)) return OTAMD_EINVAL;
-  if (rows == 0) return OTAMD_OK;
+// what every LayerNorm launcher asks of its bf16 operands: C in whole 16-byte chunks, at most LN_MAXCH per lane; row
+// strides in 16-byte units; 16-byte aligned bases
+static bool ln_args_ok(int C, std::initializer_list<long long> lds, std::initializer_list<const void*> ptrs) {
+  bool ok = C % 8 == 0 && C <= 64 * 8 * LN_MAXCH;
+  for (long long ld : lds) ok = ok && ld % 8 == 0;
+  for (const void* p : ptrs) ok = ok && ((uintptr_t)p & 15) == 0;
+  return ok;
+}
+
+// launch KERNEL<cpl> with L lanes per row: one row group of 64 / L rows per wave, 4 waves per block
+#define LN_ROWS_LAUNCH(KERNEL, cpl, L, rows, stream, ...)                        \
+  do {                                                                            \
+    const int rpb_ = 4 * (64 / (L)), nb_ = ((rows) + rpb_ - 1) / rpb_;            \
+    switch (cpl) {                                                                \
+      case 1: KERNEL<1><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;             \
+      case 2: KERNEL<2><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;             \
+      case 3: KERNEL<3><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;             \
+      case 4: KERNEL<4><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;             \
+      case 5: KERNEL<5><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;             \
+      case 6: KERNEL<6><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;             \
+      default: KERNEL<8><<<nb_, 256, 0, stream>>>(__VA_ARGS__); break;            \
+    }                                                                             \
+  } while (0)
+
+// the row kernels of each family, for every C that ln_pick fits (false: no fit, nothing launched)
+static bool ln_fwd_rows(const void* x, long long ldx, void* y, long long ldy, int rows, int C, float eps,
+                        const void* gamma, const void* beta, float* mean, float* rstd, hipStream_t stream) {
   int L = 0;
   const int cpl = ln_pick(C / 8, &L);
-  if (cpl) {
-    const int rpb = 4 * (64 / L);
-    const int nb = (rows + rpb - 1) / rpb;
-#define LNF(K) ln_fwd_rows_kernel<K><<<nb, 256, 0, stream>>>((const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, C, eps, \
-                                                            (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, L)
-    switch (cpl) {
-      case 1: LNF(1); break;
-      case 2: LNF(2); break;
-      case 3: LNF(3); break;
-      case 4: LNF(4); break;
-      case 5: LNF(5); break;
-      case 6: LNF(6); break;
-      default: LNF(8); break;
-    }
-#undef LNF
-    OTAMD_CHECK_LAUNCH();
-    return OTAMD_OK;
-  }
-  ln_fwd_kernel<<<(rows + 3) / 4, 256, 0, stream>>>((const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, C, eps,
-                                                    (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd);
+  if (!cpl) return false;
+  LN_ROWS_LAUNCH(ln_fwd_rows_kernel, cpl, L, rows, stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, C, eps,
+                 (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, L);
+  return true;
+}
+// dres: a residual gradient added to dx (nullptr: none; `accumulate` then adds the previous dx instead)
+static bool ln_bwd_rows(const void* x, long long ldx, const void* dy, long long lddy, void* dx, long long lddx,
+                        int rows, int C, const void* gamma, const float* mean, const float* rstd, int accumulate,
+                        const void* dres, long long ldres, hipStream_t stream) {
+  int L = 0;
+  const int cpl = ln_pick(C / 8, &L);
+  if (!cpl) return false;
+  LN_ROWS_LAUNCH(ln_bwd_rows_kernel, cpl, L, rows, stream, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy,
+                 (bf16_t*)dx, lddx, rows, C, (const bf16_t*)gamma, mean, rstd, accumulate, L, (const bf16_t*)dres,
+                 ldres);
+  return true;
+}
+#undef LN_ROWS_LAUNCH
+
+OTAMD_API int otamd_layernorm_fwd(const void* x, long long ldx, void* y, long long ldy, int rows, int C, float eps,
+                                  const void* gamma, const void* beta, float* mean, float* rstd, hipStream_t stream) {
+  if (!x || !y || !gamma || !beta || !mean || !rstd || rows < 0) return OTAMD_EINVAL;
+  if (!ln_args_ok(C, {ldx, ldy}, {x, y, gamma, beta})) return OTAMD_EINVAL;
+  if (rows == 0) return OTAMD_OK;
+  if (!ln_fwd_rows(x, ldx, y, ldy, rows, C, eps, gamma, beta, mean, rstd, stream))
+    ln_fwd_kernel<<<(rows + 3) / 4, 256, 0, stream>>>((const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, C, eps,
+                                                      (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }
@@ -983,27 +979,9 @@ OTAMD_API int otamd_layernorm_bwd(const void* x, long long ldx, const void* dy, 
                                   const float* rstd, void* dgamma, void* dbeta, int param_f32, int param_acc,
                                   float* part, int accumulate, hipStream_t stream) {
   // dgamma == dbeta == nullptr: frozen affine (LoRA training), no parameter-gradient reduce
-  if (!x || !dy || !dx || !gamma || !mean || !rstd || (!dgamma != !dbeta) || !part) return OTAMD_EINVAL;
-  if (rows <= 0 || C % 8 || C > 64 * 8 * LN_MAXCH || ldx % 8 || lddy % 8 || lddx % 8) return OTAMD_EINVAL;
-  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)gamma) & 15) return OTAMD_EINVAL;
-  int L = 0;
-  const int cpl = ln_pick(C / 8, &L);
-  if (cpl) {
-    const int rpb = 4 * (64 / L);
-    const int nbr = (rows + rpb - 1) / rpb;
-#define LNB(K) ln_bwd_rows_kernel<K><<<nbr, 256, 0, stream>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, \
-                                                              (bf16_t*)dx, lddx, rows, C, (const bf16_t*)gamma, mean, \
-                                                              rstd, accumulate, L)
-    switch (cpl) {
-      case 1: LNB(1); break;
-      case 2: LNB(2); break;
-      case 3: LNB(3); break;
-      case 4: LNB(4); break;
-      case 5: LNB(5); break;
-      case 6: LNB(6); break;
-      default: LNB(8); break;
-    }
-#undef LNB
+  if (!x || !dy || !dx || !gamma || !mean || !rstd || (!dgamma != !dbeta) || !part || rows <= 0) return OTAMD_EINVAL;
+  if (!ln_args_ok(C, {ldx, lddy, lddx}, {x, dy, dx, gamma})) return OTAMD_EINVAL;
+  if (ln_bwd_rows(x, ldx, dy, lddy, dx, lddx, rows, C, gamma, mean, rstd, accumulate, nullptr, 0, stream)) {
     OTAMD_CHECK_LAUNCH();
     if (!dgamma) return OTAMD_OK;
     return ln_param_grads(x, ldx, dy, lddy, rows, C, mean, rstd, dgamma, dbeta, param_f32, param_acc, part, stream);
@@ -1026,9 +1004,8 @@ OTAMD_API int otamd_layernorm_bwd(const void* x, long long ldx, const void* dy, 
 OTAMD_API int otamd_layernorm_param_grad(const void* x, long long ldx, const void* dy, long long lddy, int rows,
                                          int C, const float* mean, const float* rstd, void* dgamma, void* dbeta,
                                          int param_f32, int param_acc, float* part, hipStream_t stream) {
-  if (!x || !dy || !mean || !rstd || !dgamma || !dbeta || !part) return OTAMD_EINVAL;
-  if (rows <= 0 || C % 8 || C > 64 * 8 * LN_MAXCH || ldx % 8 || lddy % 8) return OTAMD_EINVAL;
-  if (((uintptr_t)x | (uintptr_t)dy) & 15) return OTAMD_EINVAL;
+  if (!x || !dy || !mean || !rstd || !dgamma || !dbeta || !part || rows <= 0) return OTAMD_EINVAL;
+  if (!ln_args_ok(C, {ldx, lddy}, {x, dy})) return OTAMD_EINVAL;
   return ln_param_grads(x, ldx, dy, lddy, rows, C, mean, rstd, dgamma, dbeta, param_f32, param_acc, part, stream);
 }
 
@@ -1038,27 +1015,10 @@ OTAMD_API int otamd_layernorm_param_grad(const void* x, long long ldx, const voi
 OTAMD_API int otamd_layernorm_bwd_res(const void* x, long long ldx, const void* dy, long long lddy, const void* dres,
                                       long long ldres, void* dx, long long lddx, int rows, int C, const void* gamma,
                                       const float* mean, const float* rstd, hipStream_t stream) {
-  if (!x || !dy || !dres || !dx || !gamma || !mean || !rstd) return OTAMD_EINVAL;
-  if (rows <= 0 || C % 8 || C > 64 * 8 * LN_MAXCH || ldx % 8 || lddy % 8 || lddx % 8 || ldres % 8) return OTAMD_EINVAL;
-  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dres | (uintptr_t)gamma) & 15) return OTAMD_EINVAL;
-  int L = 0;
-  const int cpl = ln_pick(C / 8, &L);
-  if (!cpl) return OTAMD_EUNSUPPORTED;
-  const int rpb = 4 * (64 / L);
-  const int nbr = (rows + rpb - 1) / rpb;
-#define LNBR(K) ln_bwd_rows_kernel<K><<<nbr, 256, 0, stream>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, \
-                                                               (bf16_t*)dx, lddx, rows, C, (const bf16_t*)gamma, mean, \
-                                                               rstd, 0, L, (const bf16_t*)dres, ldres)
-  switch (cpl) {
-    case 1: LNBR(1); break;
-    case 2: LNBR(2); break;
-    case 3: LNBR(3); break;
-    case 4: LNBR(4); break;
-    case 5: LNBR(5); break;
-    case 6: LNBR(6); break;
-    default: LNBR(8); break;
-  }
-#undef LNBR
+  if (!x || !dy || !dres || !dx || !gamma || !mean || !rstd || rows <= 0) return OTAMD_EINVAL;
+  if (!ln_args_ok(C, {ldx, lddy, lddx, ldres}, {x, dy, dx, dres, gamma})) return OTAMD_EINVAL;
+  if (!ln_bwd_rows(x, ldx, dy, lddy, dx, lddx, rows, C, gamma, mean, rstd, 0, dres, ldres, stream))
+    return OTAMD_EUNSUPPORTED;
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

@@ -57,71 +57,73 @@ def workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     return ws
 
 
-_DEFER_ARENAS: dict = {}   # raw stream -> persistent arena of its deferred split-K slabs
+_ARENAS: dict = {}   # (user, raw stream) -> persistent arena of that stream's deferred partials, held until exit
+
+
+def _defer_arena(user: str, stream, nbytes: int) -> torch.Tensor:
+    key = (user, stream.cuda_stream)
+    ar = _ARENAS.get(key)
+    if ar is None or ar.numel() < nbytes:
+        ar = _ARENAS[key] = torch.empty(nbytes, dtype=torch.uint8, device=stream.device)
+    return ar
+
+
+def _defer_call(name: str, stream, *args):
+    check(getattr(lib(), name)(C.c_void_p(stream.cuda_stream), *args), name)
+
+
+def _defer_stats(name: str, n: int, *args) -> tuple:
+    out = (C.c_longlong * n)()
+    check(getattr(lib(), name)(*args, C.cast(out, C.c_void_p)), name)
+    return tuple(int(v) for v in out)
 
 
 def defer_reduces_begin(stream, grads: torch.Tensor, nbytes: int = 256 << 20) -> None:
     """defer the split-K reduces of the weight-gradient GEMMs launched on `stream` (a torch Stream) that write into
     `grads` (the flat gradient buffer) and launch them grouped (otamd_gemm_defer_begin: bit-identical, one launch
     per up to 40 GEMMs)"""
-    key = stream.cuda_stream
-    ar = _DEFER_ARENAS.get(key)
-    if ar is None or ar.numel() < nbytes:
-        ar = _DEFER_ARENAS[key] = torch.empty(nbytes, dtype=torch.uint8, device=stream.device)
-    check(lib().otamd_gemm_defer_begin(C.c_void_p(key), _p(ar), ar.numel(), _p(grads),
-                                       grads.numel() * grads.element_size()), "otamd_gemm_defer_begin")
+    ar = _defer_arena("gemm", stream, nbytes)
+    _defer_call("otamd_gemm_defer_begin", stream, _p(ar), ar.numel(), _p(grads), grads.numel() * grads.element_size())
 
 
 def defer_reduces_flush(stream) -> None:
-    check(lib().otamd_gemm_defer_flush(C.c_void_p(stream.cuda_stream)), "otamd_gemm_defer_flush")
+    _defer_call("otamd_gemm_defer_flush", stream)
 
 
 def defer_reduces_end(stream) -> None:
-    check(lib().otamd_gemm_defer_end(C.c_void_p(stream.cuda_stream)), "otamd_gemm_defer_end")
+    _defer_call("otamd_gemm_defer_end", stream)
 
 
 def defer_reduces_stats() -> tuple:
     """(GEMMs whose split-K reduce went out deferred, grouped reduce launches) since the library loaded"""
-    out = (C.c_longlong * 2)()
-    check(lib().otamd_gemm_defer_stats(C.cast(out, C.c_void_p)), "otamd_gemm_defer_stats")
-    return int(out[0]), int(out[1])
+    return _defer_stats("otamd_gemm_defer_stats", 2)
 
 
 def defer_reduces_pending(stream) -> int:
     return int(lib().otamd_gemm_defer_pending(C.c_void_p(stream.cuda_stream)))
 
 
-_LN_DEFER_ARENAS: dict = {}
-
-
 def ln_defer_begin(stream, nbytes: int = 64 << 20) -> None:
     """defer the LayerNorm parameter-gradient reduces launched on `stream` (a torch Stream): their per-slab partials
     go to an arena and up to 64 LayerNorms' final dgamma / dbeta sums go out in one grouped launch
     (otamd_layernorm_defer_begin: bit-identical)"""
-    key = stream.cuda_stream
-    ar = _LN_DEFER_ARENAS.get(key)
-    if ar is None or ar.numel() < nbytes:
-        ar = _LN_DEFER_ARENAS[key] = torch.empty(nbytes, dtype=torch.uint8, device=stream.device)
-    check(lib().otamd_layernorm_defer_begin(C.c_void_p(key), _p(ar), ar.numel()), "otamd_layernorm_defer_begin")
+    ar = _defer_arena("layernorm", stream, nbytes)
+    _defer_call("otamd_layernorm_defer_begin", stream, _p(ar), ar.numel())
 
 
 def ln_defer_flush(stream) -> None:
-    check(lib().otamd_layernorm_defer_flush(C.c_void_p(stream.cuda_stream)), "otamd_layernorm_defer_flush")
+    _defer_call("otamd_layernorm_defer_flush", stream)
 
 
 def ln_defer_end(stream, launch=None) -> None:
     """flush and leave defer mode; launch: the stream the pending reduces go out on (ordered after `stream` by the
     caller; default `stream`)"""
-    check(lib().otamd_layernorm_defer_end_on(C.c_void_p(stream.cuda_stream),
-                                             C.c_void_p((launch or stream).cuda_stream)), "otamd_layernorm_defer_end_on")
+    _defer_call("otamd_layernorm_defer_end_on", stream, C.c_void_p((launch or stream).cuda_stream))
 
 
 def ln_defer_stats(stream) -> tuple:
     """(LayerNorms whose parameter reduce went out deferred, grouped launches, pending on `stream`)"""
-    out = (C.c_longlong * 3)()
-    check(lib().otamd_layernorm_defer_stats(C.c_void_p(stream.cuda_stream), C.cast(out, C.c_void_p)),
-          "otamd_layernorm_defer_stats")
-    return int(out[0]), int(out[1]), int(out[2])
+    return _defer_stats("otamd_layernorm_defer_stats", 3, C.c_void_p(stream.cuda_stream))
 
 
 _gemm_forced_splits = 0   # tools/gemm_splits.py probe: forces the split count of planned GEMMs
