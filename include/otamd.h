@@ -518,6 +518,17 @@ int otamd_adafactor_slab_size(void);
 /* replaces: ABI check */
 int otamd_adafactor_group_size(void);
 
+/* replaces: EMAModuleWrapper.step (modules/module/EMAModule.py:37-54), ema.add_(one_minus_decay * (parameter - ema))
+   per tensor, for elements [begin, end) of the flat buffers (multiples of 8, 16-byte aligned pointers; padding is 0
+   in both and stays 0).  Each of the three torch ops rounds to its result dtype.  form 0: ema, p bf16; 1: ema, p
+   fp32 (an fp32 store or the master of a master store); 2: ema fp32, p bf16 widened exactly (torch's promotion
+   after ema.to(dtype=float32)).  one_minus_decay: Python's double 1 - decay narrowed to fp32.  One launch. */
+int otamd_ema_range(void* ema, const void* p, int form, long long begin, long long end, float one_minus_decay,
+    hipStream_t stream);
+
+/* replaces: nothing (the elements one sweep of the grid-stride loop of form's EMA kernel covers at the grid cap) */
+int otamd_ema_sweep_elems(int form);
+
 #ifdef __cplusplus
 }
 #endif

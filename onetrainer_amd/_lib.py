@@ -130,6 +130,9 @@ SIGNATURES: dict[str, list] = {
     "otamd_adafactor_tensor_size": [],
     "otamd_adafactor_slab_size": [],
     "otamd_adafactor_group_size": [],
+    # ema.hip
+    "otamd_ema_range": [VP, VP, I, LL, LL, F, VP],
+    "otamd_ema_sweep_elems": [I],
     # norm.hip
     "otamd_groupnorm_fwd": [VP, LL, VP, LL, I, I, I, I, F, VP, VP, I, VP, VP, VP, VP, VP, VP],
     "otamd_groupnorm_bwd": [VP, LL, VP, LL, VP, LL, I, I, I, I, VP, I, VP, VP, VP, VP, VP, VP, I, I, VP, I, VP],

@@ -907,6 +907,32 @@ def adafactor_step(p, g, w, state, scratch, slab_sq, scal, tensors_dev, t_range,
           "otamd_adafactor_step")
 
 
+def ema_form(ema, p) -> int:
+    """the C-ABI form code of csrc/ema.hip: 0 bf16 shadow of bf16 parameters, 1 fp32 / fp32, 2 fp32 shadow of bf16
+    parameters."""
+    form = {(BF16, BF16): 0, (F32, F32): 1, (F32, BF16): 2}.get((ema.dtype, p.dtype))
+    _req(form is not None, "ema: bf16 / bf16, fp32 / fp32 or an fp32 shadow of bf16 parameters")
+    return form
+
+
+def ema_update(ema, p, one_minus_decay: float, begin=0, end=None):
+    """ema <- ema + one_minus_decay * (p - ema) over elements [begin, end) of the flat buffers (default: all), with
+    the three torch roundings of EMAModuleWrapper.step; one launch (csrc/ema.hip)."""
+    n = p.numel()
+    end = n if end is None else end
+    form = ema_form(ema, p)
+    for t in (ema, p):
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and _aligned(t), "ema flat buffers")
+    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0, "ema range: multiples of 8 within the store")
+    check(lib().otamd_ema_range(_p(ema), _p(p), form, begin, end, float(one_minus_decay), stream_handle()),
+          "otamd_ema_range")
+
+
+def ema_sweep_elems(form: int) -> int:
+    """elements one sweep of the grid-stride loop of form's EMA kernel covers at the grid cap"""
+    return int(lib().otamd_ema_sweep_elems(form))
+
+
 def grad_norm_dtype(grads, fp32_semantics=False):
     """the C-ABI grad_dtype code: 0 bf16, 1 fp32, 2 bf16 storage of an fp32-master network's gradients."""
     if grads.dtype == BF16:

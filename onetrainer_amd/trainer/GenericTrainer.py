@@ -197,7 +197,16 @@ class GenericTrainer(TimedActionMixin):
                             f"{tp.filename_string()}{_file_extension(cfg.output_model_format)}")
         if print_msg and self.rank == 0:
             print_cb("Saving " + path)
-        return self._write_model(path, cfg.output_model_format)
+        # GenericTrainer.py:467,494: the averaged weights are what a save holds; the trained ones wait on the host
+        # and come back whether or not the write succeeded.  Only the writing rank swaps.
+        ema = getattr(self.model, "ema", None) if self.rank == 0 else None
+        if ema is not None:
+            ema.copy_ema_to(store_temp=True)
+        try:
+            return self._write_model(path, cfg.output_model_format)
+        finally:
+            if ema is not None:
+                ema.copy_temp_to()
 
     def _write_model(self, path: str, fmt: str) -> str | None:
         import os
@@ -274,6 +283,11 @@ class GenericTrainer(TimedActionMixin):
             if self.tensorboard is not None:   # GenericTrainer.py:720-722: lr/* at this update's global_step
                 setup.report_to_tensorboard(model, cfg, self.lr_scheduler, self.tensorboard)
             setup.after_optimizer_step(model, cfg, tp)
+            if getattr(model, "ema", None) is not None:   # GenericTrainer.py:737-747, before next_step
+                update_step = tp.global_step // cfg.gradient_accumulation_steps
+                if self.tensorboard is not None:
+                    self.tensorboard.add_scalar("ema_decay", model.ema.get_current_decay(update_step), tp.global_step)
+                model.ema.step(update_step)
             self.one_step_trained = True      # GenericTrainer.py:749: only after an optimizer update
         else:
             store.accumulating = True
@@ -479,6 +493,8 @@ class GenericTrainer(TimedActionMixin):
         cfg = self.config
         if cfg.backup_before_save:
             self.backup(self.model.train_progress)
+        if getattr(self.model, "ema", None) is not None:   # GenericTrainer.py:779-780: the final, averaged model
+            self.model.ema.copy_ema_to(store_temp=False)
         path = self.final_model_path()
         if self.rank == 0:
             print("Saving " + path)

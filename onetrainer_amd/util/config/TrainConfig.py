@@ -68,6 +68,10 @@ class TrainConfig:
     learning_rate_min_factor: float = 0.0
     learning_rate_scaler: str = "NONE"
     clip_grad_norm: float | None = 1.0
+    # EMA of the trained weights (TrainConfig.py:810-812): OFF / GPU / CPU
+    ema: str = "OFF"
+    ema_decay: float = 0.999
+    ema_update_step_interval: int = 5
     # noise / timesteps (ModelSetupNoiseMixin)
     offset_noise_weight: float = 0.0
     perturbation_noise_weight: float = 0.0
@@ -134,6 +138,8 @@ class TrainConfig:
     # build-only (not in the reference): data parallel gradient bucket size / fp32 reduction
     dp_bucket_mb: int = 256
     dp_reduce_fp32: bool = False
+    # build-only: an fp32 EMA shadow of a bf16 store (module/ema.py; the reference's bf16 clone is the default)
+    ema_fp32: bool = False
     extra: dict = field(default_factory=dict)
 
     @staticmethod

@@ -19,7 +19,7 @@ import dataclasses
 from enum import Enum
 from types import SimpleNamespace
 
-BUILD_DEFAULTS = {"dp_bucket_mb": 256, "dp_reduce_fp32": False}
+BUILD_DEFAULTS = {"dp_bucket_mb": 256, "dp_reduce_fp32": False, "ema_fp32": False}
 
 
 def _is_config(v) -> bool:

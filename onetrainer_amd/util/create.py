@@ -140,3 +140,25 @@ def create_optimizer(store, groups, config):
                               relative_step=o["relative_step"], warmup_init=o["warmup_init"],
                               stochastic_rounding=bool(oc.stochastic_rounding))
     raise NotImplementedError(f"optimizer {name}: only ADAMW and ADAFACTOR are on the hot path")
+
+
+def create_ema(store, state_dict, config):
+    """the EMA of the weights in `store` for config.ema (create.py:1089-1111): OFF -> None, GPU -> a shadow beside
+    the store, CPU -> a host shadow; a saved state (ema/ema.pt of a backup) is loaded into it.  Any other mode is
+    refused by name."""
+    config = plain(config)
+    mode = str(config.ema)
+    if mode == "OFF":
+        return None
+    if mode == "GPU":
+        device = store.device
+    elif mode == "CPU":
+        device = torch.device("cpu")
+    else:
+        raise NotImplementedError(f"ema mode {mode}: OFF, GPU and CPU are supported")
+    from ..module.ema import FlatStoreEMA
+    ema = FlatStoreEMA(store, decay=config.ema_decay, update_step_interval=config.ema_update_step_interval,
+                       device=device, fp32_shadow=bool(config.ema_fp32))
+    if state_dict is not None:
+        ema.load_state_dict(state_dict)
+    return ema

@@ -51,10 +51,15 @@ def remap_optimizer_state_dict(state_dict: dict, new_state_dict: dict, new_group
 
 def restore_training_state(model, config) -> None:
     """apply what a loader left on the model (InternalModelLoaderMixin.py:16-42): the optimizer state
-    of a backup, remapped onto the groups setup_model just built."""
+    of a backup, remapped onto the groups setup_model just built, and the EMA of the trained weights
+    (create.create_ema, with the backup's ema/ema.pt when there is one)."""
     sd = getattr(model, "optimizer_state_dict", None)
     if sd is not None and model.optimizer is not None:
         name = str(config.optimizer.optimizer)
         remapped = remap_optimizer_state_dict(sd, model.optimizer.state_dict(), model.param_group_mapping, name)
         model.optimizer.load_state_dict(remapped)
         model.optimizer_state_dict = None
+    if str(getattr(config, "ema", "OFF")) != "OFF" and model.optimizer is not None:
+        from .create import create_ema
+        model.ema = create_ema(model.optimizer.store, getattr(model, "ema_state_dict", None), config)
+        model.ema_state_dict = None
