@@ -362,7 +362,7 @@ OTAMD_API int otamd_cast_f32(const float* x, void* y, long long n, int dst_f32, 
   return OTAMD_OK;
 }
 OTAMD_API int otamd_timestep_embedding(const float* t, int n, int dim, void* out, long long ldo, hipStream_t s) {
-  if (!t || !out || n <= 0 || dim % 2) return OTAMD_EINVAL;
+  if (!t || !out || n <= 0 || dim <= 0 || dim % 2 || ldo < dim) return OTAMD_EINVAL;
   timestep_embedding_kernel<<<grid_for((long long)n * dim / 2), 256, 0, s>>>(t, n, dim, (bf16_t*)out, ldo);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;

@@ -212,7 +212,7 @@ struct QKRopeArgs {
   bf16_t* y; long long ldy; int yqoff, ykoff;         // outputs (fwd: normalized + rotated; bwd: dx)
   const bf16_t* dy; long long lddy; int dyqoff, dykoff;
   const bf16_t* wq; const bf16_t* wk; const bf16_t* wq_ctx; const bf16_t* wk_ctx;
-  const float* cs; const float* sn;                   // [T][128] rotary cos / sin (repeat-interleaved)
+  const float* cs; const float* sn;                   // [T][128] rotary cos / sin, one entry per element
   float* dw_part;                                     // bwd: [blocks][4][128] (q_img, k_img, q_ctx, k_ctx) or null
   int rows, B, H, L;
   float eps;
@@ -289,7 +289,9 @@ __global__ void __launch_bounds__(256) qknorm_rope_bwd_kernel(QKRopeArgs a) {
                            __uint_as_float(xv.y << 16), __uint_as_float(xv.y & 0xffff0000u)};
       const float g0 = __uint_as_float(gv.x << 16), g1 = __uint_as_float(gv.x & 0xffff0000u);
       const float g2 = __uint_as_float(gv.y << 16), g3 = __uint_as_float(gv.y & 0xffff0000u);
-      const float dn[4] = {g0 * c4.x + g1 * s4.x, g1 * c4.y - g0 * s4.y, g2 * c4.z + g3 * s4.z, g3 * c4.w - g2 * s4.w};
+      // the transpose of the forward's 2x2 block [[c_e, -s_e], [s_o, c_o]]: the even element's gradient takes the odd
+      // entry of the sin table and the odd one the even entry (the same value in repeat-interleaved tables)
+      const float dn[4] = {g0 * c4.x + g1 * s4.y, g1 * c4.y - g0 * s4.x, g2 * c4.z + g3 * s4.w, g3 * c4.w - g2 * s4.z};
       const float ss = half_sum(xf[0] * xf[0] + xf[1] * xf[1] + xf[2] * xf[2] + xf[3] * xf[3]);
       const float rr = rsqrtf(ss * (1.f / 128.f) + a.eps);
       float xh[4], dxh[4], dot = 0.f;
@@ -525,7 +527,8 @@ OTAMD_API int otamd_gated_add_bwd(const void* dout, long long lddo, const void* 
                                   long long lddy, int rows, int D, const void* mod, long long ldm, int gate_off, int B,
                                   void* dmod, float* part, hipStream_t s) {
   if (!dout || !y || !dy || !mod || !dmod || !part || rows <= 0 || B <= 0 || rows % B || D % 8 || lddo % 8 ||
-      ldy % 8 || lddy % 8 || ldm % 8 || !a16(dout) || !a16(y) || !a16(dy))
+      ldy % 8 || lddy % 8 || ldm % 8 || gate_off % 8 || gate_off < 0 || !a16(dout) || !a16(y) || !a16(dy) || !a16(mod) ||
+      ((uintptr_t)part & 15))
     return OTAMD_EINVAL;
   const int T = rows / B, S = mod_splits(T, D, B);
   dim3 g((D / 8 + 255) / 256, B, S);
@@ -544,6 +547,8 @@ static bool qk_ok(const QKRopeArgs& a) {
   if (a.ldx % 4 || a.ldy % 4 || a.qoff % 4 || a.koff % 4 || a.yqoff % 4 || a.ykoff % 4) return false;
   if (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.cs | (uintptr_t)a.sn) & 15) return false;
   if (!a.wq_ctx != !a.wk_ctx) return false;
+  // the weights are read as 8-byte pairs of words
+  if (((uintptr_t)a.wq | (uintptr_t)a.wk | (uintptr_t)a.wq_ctx | (uintptr_t)a.wk_ctx) & 7) return false;
   return true;
 }
 
@@ -563,6 +568,8 @@ OTAMD_API int otamd_qknorm_rope_bwd(const QKRopeArgs* in, void* dwq, void* dwk, 
   QKRopeArgs a = *in;
   const bool need_dw = dwq || dwk || dwq_ctx || dwk_ctx;
   if (need_dw && !part) return OTAMD_EINVAL;
+  const uintptr_t dwmask = dw_f32 ? 3 : 1;
+  if (((uintptr_t)dwq | (uintptr_t)dwk | (uintptr_t)dwq_ctx | (uintptr_t)dwk_ctx) & dwmask) return OTAMD_EINVAL;
   a.dw_part = need_dw ? part : nullptr;
   const long long waves = 2LL * a.rows;
   const int nblk = (int)std::min<long long>((waves + 3) / 4, 1024);

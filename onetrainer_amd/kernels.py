@@ -1737,6 +1737,8 @@ def qknorm_rope_bwd(x, qoff, koff, dy, H, B, L, w, cs, sn, dx, dxqoff, dxkoff, d
     a.dy, a.lddy, a.dyqoff, a.dykoff = _p(dy), lddy, 0, H * 128
     a.y, a.ldy, a.yqoff, a.ykoff = _p(dx), lddx, dxqoff, dxkoff
     need = any(t is not None for t in dw)
+    _req(len({t.dtype for t in dw if t is not None}) <= 1 and all(t is None or t.dtype in (BF16, F32) for t in dw),
+         "q/k norm weight grads: all bf16 or all fp32")
     f32 = int(any(t is not None and t.dtype == F32 for t in dw))
     part = workspace(512 * 1024 * 4, x.device) if need else None
     check(lib().otamd_qknorm_rope_bwd(C.byref(a), *[_p(t) for t in dw], f32, int(dw_acc), _p(part), stream_handle()),
