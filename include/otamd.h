@@ -375,6 +375,30 @@ int otamd_lora_shadow(const float* src, void* dst, const void* table, int n_entr
 /* replaces: ABI check */
 int otamd_lora_shadow_entry_size(void);
 
+/* replaces: DoRAModule.forward's weight expression (modules/module/LoRAModule.py:385-412) for every adapted module in
+   one launch: n = ||W + s up down|| over every axis but the kept one (axis 0: input channels, 1: output channels)
+   + eps, written to `norms`, and W' = bf16(dora_scale * ((W + s up down) / n)) written to `wp` (0 where n == 0).
+   Weights are [out, kk * cin] matrices in store layout; fp32 accumulation in a fixed order, no atomics.
+   table: {long long w_off, wp_off, down_off, up_off, scale_off, norm_off; int out, cin, kk, rank, cblk0, rblk0;
+   float s; int pad} per module, the same array on the device and on the host (the host copy is checked against the
+   buffer sizes, in elements, on every call); cblk0 / rblk0: running sums of ceil(cin / 64) / ceil(out / 64).
+   cin % 4 == 0, rank <= otamd_dora_max_rank(). */
+int otamd_dora_merge(const void* table_dev, const void* table_host, int n, int axis, float eps, const void* base,
+    long long base_numel, const float* params, long long params_numel, float* norms, long long norms_numel, void* wp,
+    long long wp_numel, hipStream_t s);
+
+/* replaces: autograd of the same expression with the norm held constant, for table entries [e0, e1): from
+   g = dL/dW' (bf16, laid out as wp) to the fp32 gradients of lora_down, lora_up and dora_scale in `grads` (laid out
+   as params): d_down = s up^T H, d_up = s H down^T with H = (g * dora_scale) / n, d_scale = sum g * (Weff / n);
+   overwrite, or add when `accumulate` */
+int otamd_dora_project(const void* table_dev, const void* table_host, int n, int e0, int e1, int axis, const void* base,
+    long long base_numel, const float* params, float* grads, long long params_numel, const float* norms,
+    long long norms_numel, const void* g, long long g_numel, int accumulate, hipStream_t s);
+
+/* replaces: ABI checks */
+int otamd_dora_entry_size(void);
+int otamd_dora_max_rank(void);
+
 /* replaces: diffusers get_timestep_embedding (UNet time_proj / add_time_proj) */
 int otamd_timestep_embedding(const float* t, int n, int dim, void* out, long long ldo, hipStream_t s);
 

@@ -74,6 +74,13 @@ class LoraShadowEntry(C.Structure):
                 ("dst_ld", C.c_int), ("scale", C.c_float), ("transpose", C.c_int), ("pad", C.c_int)]
 
 
+class DoraEntry(C.Structure):
+    _fields_ = [("w_off", C.c_longlong), ("wp_off", C.c_longlong), ("down_off", C.c_longlong),
+                ("up_off", C.c_longlong), ("scale_off", C.c_longlong), ("norm_off", C.c_longlong),
+                ("out", C.c_int), ("cin", C.c_int), ("kk", C.c_int), ("rank", C.c_int), ("cblk0", C.c_int),
+                ("rblk0", C.c_int), ("s", C.c_float), ("pad", C.c_int)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
                 ("dout", C.c_void_p), ("delta", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p),
@@ -175,6 +182,11 @@ SIGNATURES: dict[str, list] = {
     "otamd_cast_f32": [VP, VP, LL, I, I, VP],
     "otamd_lora_shadow": [VP, VP, VP, I, VP],
     "otamd_lora_shadow_entry_size": [],
+    # dora.hip
+    "otamd_dora_merge": [VP, VP, I, I, F, VP, LL, VP, LL, VP, LL, VP, LL, VP],
+    "otamd_dora_project": [VP, VP, I, I, I, I, VP, LL, VP, VP, LL, VP, LL, VP, LL, I, VP],
+    "otamd_dora_entry_size": [],
+    "otamd_dora_max_rank": [],
     "otamd_timestep_embedding": [VP, I, I, VP, LL, VP],
     "otamd_add": [VP, VP, VP, LL, VP],
     "otamd_dp_emulate": [VP, LL, VP, LL, LL, I, LL, VP],
@@ -256,3 +268,4 @@ def check_layouts():
     assert L.otamd_adafactor_tensor_size() == C.sizeof(AdafactorTensor)
     assert L.otamd_adafactor_slab_size() == C.sizeof(AdafactorSlab)
     assert L.otamd_adafactor_group_size() == C.sizeof(AdafactorGroup)
+    assert L.otamd_dora_entry_size() == C.sizeof(DoraEntry)

@@ -1403,6 +1403,38 @@ def lora_shadow(src_f32: torch.Tensor, dst_bf16: torch.Tensor, table: torch.Tens
           "otamd_lora_shadow")
 
 
+def _dora_args(base, params, norms, buf):
+    _req(base.dtype == BF16 and buf.dtype == BF16 and params.dtype == F32 and norms.dtype == F32, "dora dtypes")
+    _req(all(t.is_cuda and t.is_contiguous() and t.dim() == 1 for t in (base, params, norms, buf)),
+         "dora buffers: flat contiguous device tensors")
+
+
+def dora_merge(table: torch.Tensor, table_host, n_entries: int, axis: int, eps: float, base: torch.Tensor,
+               params: torch.Tensor, norms: torch.Tensor, out: torch.Tensor):
+    """DoRA merge of every adapted module in one launch (otamd_dora_merge): norms <- ||W + s up down|| + eps,
+    out (W', bf16) <- dora_scale * (W + s up down) / n.  table: device bytes of _lib.DoraEntry[n_entries];
+    table_host: the same array as a ctypes object (checked against the buffer sizes by the library)."""
+    _dora_args(base, params, norms, out)
+    _req(table.dtype == torch.uint8 and table.numel() == n_entries * C.sizeof(_lib.DoraEntry), "dora table")
+    check(lib().otamd_dora_merge(_p(table), C.cast(table_host, C.c_void_p), n_entries, int(axis), float(eps), _p(base),
+                                 base.numel(), _p(params), params.numel(), _p(norms), norms.numel(), _p(out),
+                                 out.numel(), stream_handle()), "otamd_dora_merge")
+
+
+def dora_project(table: torch.Tensor, table_host, n_entries: int, e0: int, e1: int, axis: int, base: torch.Tensor,
+                 params: torch.Tensor, norms: torch.Tensor, g: torch.Tensor, out: torch.Tensor,
+                 accumulate: bool = False):
+    """DoRA gradient projection of table entries [e0, e1) (otamd_dora_project): g = dL/dW' (bf16, laid out as W') ->
+    out, the fp32 gradient buffer of the adapter store (lora_down, lora_up, dora_scale); adds when `accumulate`."""
+    _dora_args(base, params, norms, g)
+    _req(out.dtype == F32 and out.is_cuda and out.is_contiguous() and out.numel() == params.numel(), "dora grads")
+    _req(table.dtype == torch.uint8 and table.numel() == n_entries * C.sizeof(_lib.DoraEntry), "dora table")
+    check(lib().otamd_dora_project(_p(table), C.cast(table_host, C.c_void_p), n_entries, int(e0), int(e1), int(axis),
+                                   _p(base), base.numel(), _p(params), _p(out), params.numel(), _p(norms),
+                                   norms.numel(), _p(g), g.numel(), int(accumulate), stream_handle()),
+          "otamd_dora_project")
+
+
 def cast_f32_bf16(x, out=None, accumulate=False):
     """fp32 -> out (bf16 or f32), optionally out += x."""
     _req(x.dtype == F32 and x.is_contiguous(), "f32 contiguous")

@@ -2,12 +2,14 @@
 fp32 adapters on every Linear/Conv2d matching `lora_layers` (module/lora.py), parameter group
 "unet_lora" (:66-72), fused fp32 AdamW over the adapter store (create.py:509-534 with
 lora_weight_dtype FLOAT_32), shadow refresh after each update (the reference re-casts under
-autocast on every forward)."""
+autocast on every forward).  With `lora_decompose` the adapters are DoRA (module/dora.py): the same store plus
+dora_scale, and the refresh is the merge of every adapted weight."""
 from __future__ import annotations
 
 import torch
 
 from ..util.dtype_util import dtype_plan
+from ..module.dora import DoRAWrapper
 from ..module.lora import PRESETS, LoRAUNetWrapper
 from ..util.NamedParameterGroup import NamedParameterGroup, NamedParameterGroupCollection
 from ..util.create import create_optimizer
@@ -41,20 +43,30 @@ class StableDiffusionXLLoRASetup(BaseStableDiffusionXLSetup):
 
     def setup_model(self, model, config):
         config = plain(config)
-        if getattr(config, "lora_decompose", False) or config.peft_type != "LORA":
-            raise NotImplementedError("DoRA / LoHa are not on this build's hot path")
+        if config.peft_type != "LORA":
+            raise NotImplementedError("LoHa is not on this build's hot path")
+        decompose = bool(getattr(config, "lora_decompose", False))
         if config.dropout_probability and config.dropout_probability > 0:
             raise NotImplementedError("LoRA dropout > 0 is not on this build's hot path")
         if model.unet.store.trainable:
             raise ValueError("LoRA training needs a frozen base UNet (create_model(..., training_method='LORA'))")
         self.setup_optimizations(model, config)
+        if model.unet_lora is None and decompose:   # DoRA (LoRAModuleWrapper with lora_decompose): module/dora.py
+            model.unet_lora = DoRAWrapper(model.unet, rank=config.lora_rank, alpha=config.lora_alpha,
+                                          module_filter=self.layer_filter(config), seed=0,
+                                          norm_epsilon=bool(getattr(config, "lora_decompose_norm_epsilon", True)),
+                                          decompose_output_axis=bool(getattr(config, "lora_decompose_output_axis",
+                                                                             False)))
         if model.unet_lora is None:
             model.unet_lora = LoRAUNetWrapper(model.unet, rank=config.lora_rank, alpha=config.lora_alpha,
                                               module_filter=self.layer_filter(config), seed=0)
         if getattr(model, "lora_state_dict", None) is not None:   # LoRA file / backup (LoRALoaderMixin)
             model.unet_lora.load_state_dict(model.lora_state_dict)
             model.lora_state_dict = None
-        model.unet.lora = model.unet_lora
+        if isinstance(model.unet_lora, DoRAWrapper):
+            model.unet.dora = model.unet_lora
+        else:
+            model.unet.lora = model.unet_lora
         params = self.create_parameters(model, config)
         model.parameters = params
         model.optimizer = create_optimizer(model.unet_lora.store, params.parameters_for_optimizer(config), config)

@@ -113,6 +113,37 @@ def unet_fused_group(name, by_name):
     return [name]
 
 
+def discover_sites(model, rank: int, scale: float, module_filter=None) -> list:
+    """one LoraSite per base GEMM of `model` with at least one module the layer filter keeps, in forward order
+    (the site discovery LoRAWrapper and module/dora.py DoRAWrapper share)."""
+    filt = [x.strip() for x in (module_filter or []) if x.strip()]
+    allmods = module_list(model)
+    by_name = {m[0]: m for m in allmods}
+    adapted = {m[0] for m in allmods if not filt or any(f in m[0] for f in filt)}
+    group_of = getattr(model, "fused_group", unet_fused_group)
+    sites, seen = [], set()
+    for m in allmods:
+        if m[0] in seen:
+            continue
+        group = [g for g in group_of(m[0], by_name) if g in by_name]
+        seen.update(group)
+        mods = [g for g in group if g in adapted]
+        if not mods:
+            continue
+        n0, ranges = 0, {}
+        for g in group:
+            ranges[g] = (n0, n0 + by_name[g][3])
+            n0 += by_name[g][3]
+        kind = "conv" if m[1] == "conv" else "linear"
+        key = group[0] if len(group) == 1 else (group[0].rsplit(".", 1)[0] + "." + "|".join(
+            g.rsplit(".", 1)[1] for g in group))
+        sites.append(LoraSite(key=key, modules=mods, kind=kind, cin=m[2], couts=[by_name[g][3] for g in mods],
+                              k=m[4], cin_ref=m[5], couts_ref=[by_name[g][6] for g in mods], scale=scale,
+                              rank=rank, conv1x1=m[1] == "linear1x1", ranges=[ranges[g] for g in mods],
+                              n_total=n0, group=tuple(group)))
+    return sites
+
+
 class LoRAWrapper:
     """LoRAModuleWrapper(model, prefix, config, module_filter) for a HIP model (UNet or Flux
     transformer): the model supplies `specs`, `store`, `device` and optionally `fused_group(name, by_name)`."""
@@ -122,31 +153,7 @@ class LoRAWrapper:
         self.model = self.unet = model
         self.rank, self.alpha, self.prefix = rank, float(alpha), prefix
         self.scale = self.alpha / rank
-        filt = [x.strip() for x in (module_filter or []) if x.strip()]
-        allmods = module_list(model)
-        by_name = {m[0]: m for m in allmods}
-        adapted = {m[0] for m in allmods if not filt or any(f in m[0] for f in filt)}
-        group_of = getattr(model, "fused_group", unet_fused_group)
-        sites, seen = [], set()
-        for m in allmods:
-            if m[0] in seen:
-                continue
-            group = [g for g in group_of(m[0], by_name) if g in by_name]
-            seen.update(group)
-            mods = [g for g in group if g in adapted]
-            if not mods:
-                continue
-            n0, ranges = 0, {}
-            for g in group:
-                ranges[g] = (n0, n0 + by_name[g][3])
-                n0 += by_name[g][3]
-            kind = "conv" if m[1] == "conv" else "linear"
-            key = group[0] if len(group) == 1 else (group[0].rsplit(".", 1)[0] + "." + "|".join(
-                g.rsplit(".", 1)[1] for g in group))
-            sites.append(LoraSite(key=key, modules=mods, kind=kind, cin=m[2], couts=[by_name[g][3] for g in mods],
-                                  k=m[4], cin_ref=m[5], couts_ref=[by_name[g][6] for g in mods], scale=self.scale,
-                                  rank=rank, conv1x1=m[1] == "linear1x1", ranges=[ranges[g] for g in mods],
-                                  n_total=n0, group=tuple(group)))
+        sites = discover_sites(model, rank, self.scale, module_filter)
         self.sites = sites
         self.site_of = {}
         for s in sites:

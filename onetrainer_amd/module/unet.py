@@ -236,6 +236,7 @@ class UNet2DConditionModel:
                                     dtype, self.device, trainable=trainable, master=master)
         self._refs: dict = {}
         self.lora = None      # module/lora.py LoRAUNetWrapper when training adapters on a frozen base
+        self.dora = None      # module/dora.py DoRAWrapper instead, with lora_decompose: adapted GEMMs read merged weights
         if seed is not None:
             self.init_weights(seed)
 
@@ -303,6 +304,10 @@ class UNet2DConditionModel:
                 self._assign(name, sd[name].to(self.device, torch.float32), kinds[name])
 
     def R(self, names, shape=None) -> Fn.PRef:
+        if self.dora is not None:   # an adapted base GEMM runs on its merged weight W' (module/dora.py DoraRef)
+            r = self.dora.ref_for(names, shape)
+            if r is not None:
+                return r
         key = (tuple(names) if isinstance(names, (list, tuple)) else names, shape)
         r = self._refs.get(key)
         if r is None:
@@ -353,8 +358,8 @@ class UNet2DConditionModel:
         (grid.y = block): each block's fused [2C, ctx] weight sits at the same stride in the flat store.
         The reference runs one [B*77, 2C] GEMM per block (70 per SDXL forward, ~25 us each at M = 308);
         this is 11 launches.  Backward stays per block (PrecomputedLinearFn).  None when not applicable
-        (LoRA on the projection, a single block, irregular layout)."""
-        if depth < 2 or self.lora is not None:
+        (LoRA / DoRA on the projection, a single block, irregular layout)."""
+        if depth < 2 or self.lora is not None or self.dora is not None:
             return None
         names = [(f"{p}.transformer_blocks.{k}.attn2.to_k.weight", f"{p}.transformer_blocks.{k}.attn2.to_v.weight")
                  for k in range(depth)]

@@ -103,7 +103,9 @@ class TrainConfig:
     lora_weight_dtype: str = "FLOAT_32"
     lora_layers: str = ""
     lora_layer_preset: str | None = None
-    lora_decompose: bool = False
+    lora_decompose: bool = False              # DoRA (module/dora.py)
+    lora_decompose_norm_epsilon: bool = True
+    lora_decompose_output_axis: bool = False
     peft_type: str = "LORA"
     dropout_probability: float = 0.0          # LoRA dropout (TrainConfig.py:828)
     # parts
