@@ -117,6 +117,16 @@ typedef struct AdafactorGroup {
   int scale_parameter, pad;
 } AdafactorGroup;
 
+/* CAME (csrc/came.hip): the Adafactor tables above plus a fold table.  CameFold: kind 0 the global rows
+   [i0, i1), kind 1 the global columns [i0, i1) of a mode 2 tensor (at most 256, a thread each), kind 2 the
+   matrix i0 whose row-state mean is due */
+typedef struct CameGroup {
+  float lr, alpha_wd, eps1, eps2, clip_threshold;
+  float beta1, one_minus_beta1, beta2, one_minus_beta2, beta3, one_minus_beta3;
+  int pad;
+} CameGroup;
+typedef struct CameFold { long long i0, i1; int tensor, kind; } CameFold;
+
 /* replaces: diffusers Linear/Conv2d fwd+bwd inside model.unet(...) (modules/modelSetup/BaseStableDiffusionXLSetup.py:268-273); conv/linear dgrad/wgrad of loss.backward() (modules/trainer/GenericTrainer.py:693-696) */
 int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long long ws_bytes, hipStream_t stream);
 
@@ -541,6 +551,29 @@ int otamd_adafactor_tensor_size(void);
 int otamd_adafactor_slab_size(void);
 /* replaces: ABI check */
 int otamd_adafactor_group_size(void);
+
+/* replaces: CAME(params, lr, betas, weight_decay, eps, stochastic_rounding) (modules/util/create.py:938-951), its
+   step CAME.step_parameter (modules/util/optimizer/CAME.py:79-178) for every tensor [t_begin, t_end) of the
+   Adafactor tensor table, their slabs [s_begin, s_end), their fold entries [f_begin, f_end) (kinds 0, 1) and their
+   row-mean entries [r_begin, r_end) (kind 2) of the fold table: factored second moments with a constant beta2,
+   update clipping by rms(u) / clip_threshold, the fp32 first moment m (indexed as the store), the factored
+   instability (u - m)^2 + eps2 with beta3 scaling m into the update, weight decay.  form 0: p, g bf16
+   (round-to-nearest after each of the reference's two adds, or one stochastic rounding with the AdamW dither);
+   1: p, g fp32; 2: p the fp32 master, g bf16, w16 the bf16 working copy rewritten as rne(p).  state_sq /
+   state_res: fp32 row / column states of the second moment (and the full one of ndim < 2) and of the
+   instability, indexed by the same table offsets; scratch_sq / scratch_res: their fp32 partial sums; slab_sq:
+   double[slabs]; scal: float[tensors] (rms(u)); clip_coef: the pending global-norm clip (device scalar,
+   nullable).  Nine launches (seven when no matrix spans slabs), no atomics. */
+int otamd_came_step(void* p, const void* g, void* w16, int form, float* m, float* state_sq, float* state_res,
+    float* scratch_sq, float* scratch_res, double* slab_sq, float* scal, const void* tensors, int t_begin, int t_end,
+    const void* slabs, int s_begin, int s_end, const void* fold, int f_begin, int f_end, int r_begin, int r_end,
+    const CameGroup* groups, int n_groups, const float* clip_coef, int stochastic_rounding, unsigned long long seed,
+    hipStream_t stream);
+
+/* replaces: ABI check */
+int otamd_came_group_size(void);
+/* replaces: ABI check */
+int otamd_came_fold_size(void);
 
 /* replaces: EMAModuleWrapper.step (modules/module/EMAModule.py:37-54), ema.add_(one_minus_decay * (parameter - ema))
    per tensor, for elements [begin, end) of the flat buffers (multiples of 8, 16-byte aligned pointers; padding is 0

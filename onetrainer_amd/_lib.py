@@ -69,6 +69,17 @@ class AdafactorGroup(C.Structure):
                 ("one_minus_beta2t", C.c_float), ("scale_parameter", C.c_int), ("pad", C.c_int)]
 
 
+class CameGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("alpha_wd", C.c_float), ("eps1", C.c_float), ("eps2", C.c_float),
+                ("clip_threshold", C.c_float), ("beta1", C.c_float), ("one_minus_beta1", C.c_float),
+                ("beta2", C.c_float), ("one_minus_beta2", C.c_float), ("beta3", C.c_float),
+                ("one_minus_beta3", C.c_float), ("pad", C.c_int)]
+
+
+class CameFold(C.Structure):
+    _fields_ = [("i0", C.c_longlong), ("i1", C.c_longlong), ("tensor", C.c_int), ("kind", C.c_int)]
+
+
 class LoraShadowEntry(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("rows", C.c_int), ("cols", C.c_int),
                 ("dst_ld", C.c_int), ("scale", C.c_float), ("transpose", C.c_int), ("pad", C.c_int)]
@@ -137,6 +148,11 @@ SIGNATURES: dict[str, list] = {
     "otamd_adafactor_tensor_size": [],
     "otamd_adafactor_slab_size": [],
     "otamd_adafactor_group_size": [],
+    # came.hip
+    "otamd_came_step": [VP, VP, VP, I, VP, VP, VP, VP, VP, VP, VP, VP, I, I, VP, I, I, VP, I, I, I, I,
+                        C.POINTER(CameGroup), I, VP, I, C.c_ulonglong, VP],
+    "otamd_came_group_size": [],
+    "otamd_came_fold_size": [],
     # ema.hip
     "otamd_ema_range": [VP, VP, I, LL, LL, F, VP],
     "otamd_ema_sweep_elems": [I],
@@ -268,4 +284,6 @@ def check_layouts():
     assert L.otamd_adafactor_tensor_size() == C.sizeof(AdafactorTensor)
     assert L.otamd_adafactor_slab_size() == C.sizeof(AdafactorSlab)
     assert L.otamd_adafactor_group_size() == C.sizeof(AdafactorGroup)
+    assert L.otamd_came_group_size() == C.sizeof(CameGroup)
+    assert L.otamd_came_fold_size() == C.sizeof(CameFold)
     assert L.otamd_dora_entry_size() == C.sizeof(DoraEntry)

@@ -907,6 +907,43 @@ def adafactor_step(p, g, w, state, scratch, slab_sq, scal, tensors_dev, t_range,
           "otamd_adafactor_step")
 
 
+def came_step(p, g, w, m, state_sq, state_res, scratch_sq, scratch_res, slab_sq, scal, tensors_dev, t_range, slabs_dev,
+              s_range, fold_dev, f_range, r_range, groups, clip_coef=None, stochastic_rounding=False, seed=0):
+    """one fused CAME step (csrc/came.hip) over the tensors t_range, slabs s_range, fold entries f_range and row-mean
+    entries r_range of the device tables.  p / g as for adafactor_step; m: the fp32 first moment, indexed as the
+    store; state_sq / state_res and scratch_sq / scratch_res: the second-moment and instability states and their
+    partials, pairwise of one size.  The tables name element ranges of these buffers: the caller built and checked
+    them (util/optimizer/came_fused.py)."""
+    n = p.numel()
+    _req(p.dtype in (BF16, F32) and g.dtype in (BF16, F32), "came flat buffers: bf16 or fp32")
+    if w is not None:
+        form = 2
+        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, "came master: fp32 p, bf16 g and w")
+    else:
+        form = 0 if p.dtype == BF16 else 1
+        _req(g.dtype == p.dtype, "came: gradients in the store's dtype")
+    for t in (p, g, m) + ((w,) if w is not None else ()):
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "came flat buffers")
+    for t in (m, state_sq, state_res, scratch_sq, scratch_res, scal):
+        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), "came fp32 buffers")
+    _req(state_sq.numel() == state_res.numel() and scratch_sq.numel() == scratch_res.numel(),
+         "came: the instability buffers have the sizes of the second-moment buffers")
+    nt, ns = tensors_dev.numel() // C.sizeof(_lib.AdafactorTensor), slabs_dev.numel() // C.sizeof(_lib.AdafactorSlab)
+    nf = fold_dev.numel() // C.sizeof(_lib.CameFold)
+    _req(slab_sq.is_cuda and slab_sq.dtype == torch.float64 and slab_sq.numel() >= ns, "slab_sq f64[slabs]")
+    _req(scal.numel() >= nt, "scal f32[tensors]")
+    _req(0 <= t_range[0] <= t_range[1] <= nt and 0 <= s_range[0] <= s_range[1] <= ns, "came table ranges")
+    _req(0 <= f_range[0] <= f_range[1] <= nf and 0 <= r_range[0] <= r_range[1] <= nf, "came fold table ranges")
+    _req(1 <= len(groups) <= 8, "came: 1..8 parameter groups")
+    arr = (_lib.CameGroup * len(groups))(*groups)
+    check(lib().otamd_came_step(_p(p), _p(g), _p(w), form, _p(m), _p(state_sq), _p(state_res), _p(scratch_sq),
+                                _p(scratch_res), _p(slab_sq), _p(scal), _p(tensors_dev), t_range[0], t_range[1],
+                                _p(slabs_dev), s_range[0], s_range[1], _p(fold_dev), f_range[0], f_range[1],
+                                r_range[0], r_range[1], arr, len(groups), _p(clip_coef), int(stochastic_rounding),
+                                seed & 0xFFFFFFFFFFFFFFFF, stream_handle()),
+          "otamd_came_step")
+
+
 def ema_form(ema, p) -> int:
     """the C-ABI form code of csrc/ema.hip: 0 bf16 shadow of bf16 parameters, 1 fp32 / fp32, 2 fp32 shadow of bf16
     parameters."""

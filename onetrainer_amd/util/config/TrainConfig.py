@@ -26,6 +26,8 @@ class OptimizerConfig:
     scale_parameter: bool | None = None
     relative_step: bool | None = None
     warmup_init: bool | None = None
+    # CAME (None resolves as modules/util/create.py:944-949 does)
+    beta3: float | None = None
     stochastic_rounding: bool = True
     fused_back_pass: bool = False
     foreach: bool | None = False

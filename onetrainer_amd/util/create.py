@@ -1,5 +1,5 @@
 """Factories (mirrors the parts of modules/util/create.py the hot path uses:
-create_model_setup 285-353, create_optimizer 509-534 (ADAMW) and 914-936 (ADAFACTOR), create_lr_scheduler
+create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
 1114-1232, create_noise_scheduler 1235-1373)."""
 from __future__ import annotations
 
@@ -114,9 +114,19 @@ def adafactor_options(oc) -> dict:
                 relative_step=pick("relative_step", True), warmup_init=pick("warmup_init", False))
 
 
+def came_options(oc) -> dict:
+    """OptimizerConfig -> CAME arguments, None resolved exactly as create.py:944-949 resolves it (clip_threshold is
+    not passed there: it stays the class default 1.0)."""
+    def pick(name, default):
+        v = getattr(oc, name, None)
+        return v if v is not None else default
+    return dict(eps=pick("eps", 1e-30), eps2=pick("eps2", 1e-16), beta1=pick("beta1", 0.9), beta2=pick("beta2", 0.999),
+                beta3=pick("beta3", 0.9999), weight_decay=pick("weight_decay", 0))
+
+
 def create_optimizer(store, groups, config):
     """the fused optimizer over `store` for config.optimizer (create.py:509-534 ADAMW + patch_adamw, 914-936
-    ADAFACTOR + patch_adafactor).  Anything else is refused: there is no eager fall-back."""
+    ADAFACTOR + patch_adafactor, 938-951 CAME).  Anything else is refused: there is no eager fall-back."""
     config = plain(config)
     oc = config.optimizer
     name = str(oc.optimizer)
@@ -139,7 +149,13 @@ def create_optimizer(store, groups, config):
                               weight_decay=o["weight_decay"], scale_parameter=o["scale_parameter"],
                               relative_step=o["relative_step"], warmup_init=o["warmup_init"],
                               stochastic_rounding=bool(oc.stochastic_rounding))
-    raise NotImplementedError(f"optimizer {name}: only ADAMW and ADAFACTOR are on the hot path")
+    if name == "CAME":
+        from .optimizer.came_fused import FusedCAME
+        o = came_options(oc)
+        return FusedCAME(store, groups, lr=config.learning_rate, eps=(o["eps"], o["eps2"]),
+                         betas=(o["beta1"], o["beta2"], o["beta3"]), weight_decay=o["weight_decay"],
+                         stochastic_rounding=bool(oc.stochastic_rounding))
+    raise NotImplementedError(f"optimizer {name}: only ADAMW, ADAFACTOR and CAME are on the hot path")
 
 
 def create_ema(store, state_dict, config):
