@@ -26,7 +26,10 @@
 //
 // Arithmetic: fp32 element ops in the reference's order (-ffp-contract=off; the fused multiply-adds are the
 // ones torch's CPU add_(alpha=) kernels use), fp32 sums.  tests/_oracle_adafactor.py restates it.
-#include "adafactor_walk.h"   // tables, masked loads, af_clip, block sum, the slab walk (shared with came.hip)
+//
+// The unorm kernel, the slab walk, the parameter write and the EMA are shared with came.hip and live in
+// adafactor_walk.h.  The statistics kernel is not: came_stats_kernel (came.hip) restates its three-mode body.
+#include "adafactor_walk.h"
 
 struct AdafactorGroup {
   float lr;
@@ -38,10 +41,6 @@ struct AdafactorGroup {
   int pad;
 };
 struct AdafactorGroups { AdafactorGroup g[AF_MAX_GROUPS]; };
-
-__device__ __forceinline__ float af_ema(float state, float mean, const AdafactorGroup& G) {
-  return fmaf(mean, G.one_minus_beta2t, state * G.beta2t);   // state.mul_(beta2t).add_(mean, alpha=1 - beta2t)
-}
 
 // ---- 1: statistics --------------------------------------------------------------------------------------------
 template <typename TP, typename TG, bool BFROUND>
@@ -70,7 +69,7 @@ __global__ void __launch_bounds__(AF_THREADS) af_stats_kernel(const TP* __restri
       const float g = af_clip<BFROUND>(af_load1<TG>(Gr, T.offset + i), coef, clip);
       const float upd = g * g + G.eps1;
       float* v = state + T.full_off + i;
-      *v = af_ema(*v, upd, G);
+      *v = af_ema(*v, upd, G.beta2t, G.one_minus_beta2t);
       if (scale) {
         const float p = af_load1<TP>(P, T.offset + i);
         pacc += (double)(p * p);
@@ -107,7 +106,7 @@ __global__ void __launch_bounds__(AF_THREADS) af_stats_kernel(const TP* __restri
         float s = 0.f;
         for (int c = 0; c < T.cols; ++c) s += x[c] * x[c] + G.eps1;
         float* rs = state + T.row_off + ms * T.rows + i;
-        const float nv = af_ema(*rs, s / (float)T.cols, G);
+        const float nv = af_ema(*rs, s / (float)T.cols, G.beta2t, G.one_minus_beta2t);
         *rs = nv;
         s_acc[i] = nv;
       }
@@ -120,7 +119,7 @@ __global__ void __launch_bounds__(AF_THREADS) af_stats_kernel(const TP* __restri
           s += g * g + G.eps1;
         }
         float* cs = state + T.col_off + ms * T.cols + i;
-        *cs = af_ema(*cs, s / (float)T.rows, G);
+        *cs = af_ema(*cs, s / (float)T.rows, G.beta2t, G.one_minus_beta2t);
       }
       __syncthreads();
       for (int m = tid; m < nm; m += AF_THREADS) {   // mean of the matrix's fresh row states
@@ -203,7 +202,7 @@ __global__ void __launch_bounds__(1024) af_fold_kernel(float* __restrict__ state
     float s = 0.f;
     for (int j = 0; j < T.col_tiles; ++j) s += scratch[T.rpart_off + i * T.col_tiles + j];
     float* rs = state + T.row_off + i;
-    *rs = af_ema(*rs, s / (float)T.cols, G);
+    *rs = af_ema(*rs, s / (float)T.cols, G.beta2t, G.one_minus_beta2t);
   }
   for (long long i = threadIdx.x; i < ncol; i += blockDim.x) {
     const long long b = i / T.cols;
@@ -211,7 +210,7 @@ __global__ void __launch_bounds__(1024) af_fold_kernel(float* __restrict__ state
     float s = 0.f;
     for (int k = 0; k < T.row_slabs; ++k) s += scratch[T.cpart_off + (b * T.row_slabs + k) * T.cols + c];
     float* cs = state + T.col_off + i;
-    *cs = af_ema(*cs, s / (float)T.rows, G);
+    *cs = af_ema(*cs, s / (float)T.rows, G.beta2t, G.one_minus_beta2t);
   }
   __threadfence_block();
   __syncthreads();
@@ -224,36 +223,7 @@ __global__ void __launch_bounds__(1024) af_fold_kernel(float* __restrict__ state
   }
 }
 
-// ---- 3: sum u^2 per slab ----------------------------------------------------------------------------------------
-template <typename TG, bool BFROUND>
-__global__ void __launch_bounds__(AF_THREADS) af_unorm_kernel(const TG* __restrict__ Gr, const float* __restrict__ state,
-                                                              const float* __restrict__ scratch,
-                                                              double* __restrict__ slab_sq,
-                                                              const AdafactorTensor* __restrict__ tensors,
-                                                              const AdafactorSlab* __restrict__ slabs, int s0,
-                                                              const float* __restrict__ clip_coef) {
-  __shared__ float s_r[AF_STAGE];
-  __shared__ float s_c[AF_STAGE];
-  __shared__ double s_red[4];
-  const int si = s0 + blockIdx.x;
-  const AdafactorSlab sl = slabs[si];
-  const AdafactorTensor T = tensors[sl.tensor];
-  const bool clip = clip_coef != nullptr;
-  const float coef = clip ? clip_coef[0] : 1.f;
-  double acc = 0.0;
-  af_walk<TG, BFROUND>(Gr, state, scratch, T, sl, coef, clip, s_r, s_c,
-                       [&](long long, const float* g, const float* fac, unsigned valid) {
-                         float s = 0.f;
-#pragma unroll
-                         for (int j = 0; j < 8; ++j) {
-                           const float u = fac[j] * g[j];
-                           if (valid >> j & 1) s = fmaf(u, u, s);
-                         }
-                         acc += (double)s;
-                       });
-  const double t = af_block_sum_d(acc, s_red);
-  if (threadIdx.x == 0) slab_sq[2 * (long long)si + 1] = t;
-}
+// ---- 3: sum u^2 per slab: af_unorm_kernel<AdafactorGroup, ...> (adafactor_walk.h) -> slab_sq[2 s + 1] ----------
 
 // ---- 4: per-tensor scalars: the slab sums in slab order -> scal[4 t] = rms(p), scal[4 t + 1] = rms(u) --------
 __global__ void af_scalars_kernel(const double* __restrict__ slab_sq, float* __restrict__ scal,
@@ -307,37 +277,9 @@ __global__ void __launch_bounds__(AF_THREADS) af_apply_kernel(TP* __restrict__ P
                              u = u * lr;
                              float x = p[j];
                              if (decay) x = fmaf(x, alpha, x);   // p.add_(p, alpha=-weight_decay * lr)
-                             x = x - u;                          // p.add_(-update)
-                             if constexpr (FORM == 0) {
-                               if (sr) {
-                                 const uint32_t bits = (__float_as_uint(x) + sr_bits(k, (uint64_t)(v + j))) & 0xFFFF0000u;
-                                 x = __uint_as_float(bits);
-                               } else {
-                                 x = rbf(x);
-                               }
-                             }
-                             p[j] = x;
+                             p[j] = x - u;                       // p.add_(-update)
                            }
-                           if (valid == 0xFFu) {
-                             if constexpr (FORM == 0) {
-                               *reinterpret_cast<bf8*>(P + v) = pack8(p);
-                             } else {
-                               *reinterpret_cast<float4*>(P + v) = make_float4(p[0], p[1], p[2], p[3]);
-                               *reinterpret_cast<float4*>(P + v + 4) = make_float4(p[4], p[5], p[6], p[7]);
-                               if constexpr (FORM == 2) *reinterpret_cast<bf8*>(W + v) = pack8(p);
-                             }
-                           } else {
-#pragma unroll
-                             for (int j = 0; j < 8; ++j)
-                               if (valid >> j & 1) {
-                                 if constexpr (FORM == 0) {
-                                   reinterpret_cast<bf16_t*>(P)[v + j] = f2bf(p[j]);
-                                 } else {
-                                   reinterpret_cast<float*>(P)[v + j] = p[j];
-                                   if constexpr (FORM == 2) W[v + j] = f2bf(p[j]);
-                                 }
-                               }
-                           }
+                           af_write_params<FORM>(P, W, v, p, valid, sr, k);
                          });
 }
 
@@ -357,8 +299,8 @@ static int af_launch(void* p, const void* g, void* w, float* state, float* scrat
   OTAMD_CHECK_LAUNCH();
   af_fold_kernel<<<nt, 1024, 0, stream>>>(state, scratch, tensors, t0, G);
   OTAMD_CHECK_LAUNCH();
-  af_unorm_kernel<TG, FORM == 0><<<ns, AF_THREADS, 0, stream>>>((const TG*)g, state, scratch, slab_sq, tensors, slabs, s0,
-                                                                clip_coef);
+  af_unorm_kernel<AdafactorGroup, TG, FORM == 0><<<ns, AF_THREADS, 0, stream>>>((const TG*)g, state, scratch, slab_sq, 2, 1,
+                                                                                tensors, slabs, s0, clip_coef);
   OTAMD_CHECK_LAUNCH();
   af_scalars_kernel<<<(nt + 255) / 256, 256, 0, stream>>>(slab_sq, scal, tensors, t0, t1, G);
   OTAMD_CHECK_LAUNCH();

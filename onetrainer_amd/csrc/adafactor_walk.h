@@ -1,6 +1,9 @@
 // What the factored optimizers (adafactor.hip, came.hip) share: the tensor and slab tables, the masked 16-byte
-// loads, the pending-clip rounding, the fixed-order block sum and the slab walk that hands every 8-aligned vector
-// of a slab to a body with its rsqrt factors.  adafactor.hip's header comment describes the layout and the modes.
+// loads and stores, the pending-clip rounding, the EMA, the fixed-order block sum, and, each written once here:
+//   af_walk          every 8-aligned vector of a slab with its rsqrt factors (af_unorm_kernel and the apply kernels)
+//   af_unorm_kernel  sum u^2 per slab, one template that each file instantiates under its own tag
+//   af_write_params  the parameter write of the apply kernels: bf16 rounding and the masked store of the three forms
+// The statistics kernels stay in the two .hip files.  adafactor.hip's header comment describes the layout and the modes.
 #pragma once
 #include "common.h"
 
@@ -59,6 +62,48 @@ __device__ __forceinline__ double af_block_sum_d(double v, double* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
+}
+
+// state.mul_(beta).add_(mean, alpha=1 - beta)
+__device__ __forceinline__ float af_ema(float state, float mean, float beta, float omb) {
+  return fmaf(mean, omb, state * beta);
+}
+
+// eight values at an 8-aligned element index; partial vectors element-wise (neighbouring slabs never write the
+// same bytes)
+__device__ __forceinline__ void af_store8(float* base, long long v, const float* x, unsigned valid) {
+  if (valid == 0xFFu) {
+    *reinterpret_cast<float4*>(base + v) = make_float4(x[0], x[1], x[2], x[3]);
+    *reinterpret_cast<float4*>(base + v + 4) = make_float4(x[4], x[5], x[6], x[7]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (valid >> j & 1) base[v + j] = x[j];
+  }
+}
+__device__ __forceinline__ void af_store8(bf16_t* base, long long v, const float* x, unsigned valid) {
+  if (valid == 0xFFu) {
+    *reinterpret_cast<bf8*>(base + v) = pack8(x);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (valid >> j & 1) base[v + j] = f2bf(x[j]);
+  }
+}
+
+// ---- the parameter write of an apply kernel -----------------------------------------------------------------------
+// FORM 0: bf16 store, x rounded here (stochastic bits of key k at the store index, or RNE); 1: fp32 store; 2: fp32
+// master + bf16 working copy W = rne(master)
+template <int FORM, typename TP>
+__device__ __forceinline__ void af_write_params(TP* P, bf16_t* W, long long v, float* x, unsigned valid, int sr,
+                                                uint32_t k) {
+  if constexpr (FORM == 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      x[j] = sr ? __uint_as_float((__float_as_uint(x[j]) + sr_bits(k, (uint64_t)(v + j))) & 0xFFFF0000u) : rbf(x[j]);
+  }
+  af_store8(P, v, x, valid);
+  if constexpr (FORM == 2) af_store8(W, v, x, valid);
 }
 
 // ---- the walk: every 8-aligned vector of a slab with its gradient and factors -----------------------------------
@@ -150,4 +195,36 @@ __device__ __forceinline__ void af_walk(const TG* __restrict__ Gr, const float* 
       body(v, g, fac, valid);
     }
   }
+}
+
+// ---- sum u^2 per slab, u recomputed from g and the fresh states: slab_sq[stride * slab + slot] ---------------------
+// OWNER: a type of the including file (its group struct), so that each .hip registers a kernel of its own name
+template <typename OWNER, typename TG, bool BFROUND>
+__global__ void __launch_bounds__(AF_THREADS) af_unorm_kernel(const TG* __restrict__ Gr, const float* __restrict__ state,
+                                                              const float* __restrict__ scratch,
+                                                              double* __restrict__ slab_sq, int stride, int slot,
+                                                              const AdafactorTensor* __restrict__ tensors,
+                                                              const AdafactorSlab* __restrict__ slabs, int s0,
+                                                              const float* __restrict__ clip_coef) {
+  __shared__ float s_r[AF_STAGE];
+  __shared__ float s_c[AF_STAGE];
+  __shared__ double s_red[4];
+  const int si = s0 + blockIdx.x;
+  const AdafactorSlab sl = slabs[si];
+  const AdafactorTensor T = tensors[sl.tensor];
+  const bool clip = clip_coef != nullptr;
+  const float coef = clip ? clip_coef[0] : 1.f;
+  double acc = 0.0;
+  af_walk<TG, BFROUND>(Gr, state, scratch, T, sl, coef, clip, s_r, s_c,
+                       [&](long long, const float* g, const float* fac, unsigned valid) {
+                         float s = 0.f;
+#pragma unroll
+                         for (int j = 0; j < 8; ++j) {
+                           const float u = fac[j] * g[j];
+                           if (valid >> j & 1) s = fmaf(u, u, s);
+                         }
+                         acc += (double)s;
+                       });
+  const double t = af_block_sum_d(acc, s_red);
+  if (threadIdx.x == 0) slab_sq[stride * (long long)si + slot] = t;
 }

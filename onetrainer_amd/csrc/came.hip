@@ -17,6 +17,10 @@
 //               decay, parameter write (bf16 RNE or stochastic, fp32, fp32 master + bf16 working copy)
 // Every reduction has a fixed order (no atomics): two runs give the same bits.
 //
+// Shared with adafactor.hip, in adafactor_walk.h: the unorm kernel of pass 4, the slab walk and the parameter write
+// of pass 9, the masked fp32 store, the EMA.  The statistics kernel of passes 1 and 6 restates af_stats_kernel's
+// three-mode body (sharing it cost 0.4 ms a step through code placement).
+//
 // Tables.  The Adafactor tensor and slab tables, unchanged (adafactor_walk.h; adafactor.hip describes the three
 // modes).  The second-moment and the instability factors live in two fp32 state buffers indexed by the same
 // row_off / col_off (full_off is used in the first only), their partial sums and row-state means in two scratch
@@ -48,24 +52,6 @@ struct CameFold {
   int tensor;
   int kind;
 };
-
-// state.mul_(beta).add_(mean, alpha=1 - beta)
-__device__ __forceinline__ float came_ema(float state, float mean, float beta, float omb) {
-  return fmaf(mean, omb, state * beta);
-}
-
-// eight fp32 at an 8-aligned element index; partial vectors element-wise (neighbouring slabs never write the
-// same bytes)
-__device__ __forceinline__ void came_store8(float* base, long long v, const float* x, unsigned valid) {
-  if (valid == 0xFFu) {
-    *reinterpret_cast<float4*>(base + v) = make_float4(x[0], x[1], x[2], x[3]);
-    *reinterpret_cast<float4*>(base + v + 4) = make_float4(x[4], x[5], x[6], x[7]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (valid >> j & 1) base[v + j] = x[j];
-  }
-}
 
 // ---- 1 and 6: statistics ------------------------------------------------------------------------------------------
 // PASS 0: x = g, statistic x^2 + eps1, beta2, written to the second-moment buffers (state, scratch).
@@ -109,7 +95,7 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
       m[j] = fmaf(u, G.one_minus_beta1, m[j] * G.beta1);   // exp_avg.mul_(beta1).add_(update, alpha=1 - beta1)
       x[j] = u - m[j];
     }
-    came_store8(M, v, m, valid);
+    af_store8(M, v, m, valid);
   };
 
   if (T.mode == 0) {
@@ -117,7 +103,7 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
       const float g = af_clip<BFROUND>(af_load1<TG>(Gr, T.offset + i), coef, clip);
       if constexpr (PASS == 0) {
         float* v = state + T.full_off + i;
-        *v = came_ema(*v, g * g + eps, beta, omb);
+        *v = af_ema(*v, g * g + eps, beta, omb);
       } else {   // no instability state: the update is m
         float u = af_rsqrt(fstate[T.full_off + i]) * g;
         u = u / denom;
@@ -181,7 +167,7 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
         float s = 0.f;
         for (int c = 0; c < T.cols; ++c) s += x[c] * x[c] + eps;
         float* rs = state + T.row_off + ms * T.rows + i;
-        const float nv = came_ema(*rs, s / (float)T.cols, beta, omb);
+        const float nv = af_ema(*rs, s / (float)T.cols, beta, omb);
         *rs = nv;
         s_acc[i] = nv;
       }
@@ -194,7 +180,7 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
           s += g * g + eps;
         }
         float* cs = state + T.col_off + ms * T.cols + i;
-        *cs = came_ema(*cs, s / (float)T.rows, beta, omb);
+        *cs = af_ema(*cs, s / (float)T.rows, beta, omb);
       }
       __syncthreads();
       for (int m = tid; m < nm; m += AF_THREADS) {   // mean of the matrix's fresh row states
@@ -289,14 +275,14 @@ __global__ void __launch_bounds__(AF_THREADS) came_fold_kernel(float* __restrict
     float s = 0.f;
     for (int j = 0; j < T.col_tiles; ++j) s += scratch[T.rpart_off + i * T.col_tiles + j];
     float* rs = state + T.row_off + i;
-    *rs = came_ema(*rs, s / (float)T.cols, beta, omb);
+    *rs = af_ema(*rs, s / (float)T.cols, beta, omb);
   } else {
     const long long b = i / T.cols;
     const int c = (int)(i - b * T.cols);
     float s = 0.f;
     for (int k = 0; k < T.row_slabs; ++k) s += scratch[T.cpart_off + (b * T.row_slabs + k) * T.cols + c];
     float* cs = state + T.col_off + i;
-    *cs = came_ema(*cs, s / (float)T.rows, beta, omb);
+    *cs = af_ema(*cs, s / (float)T.rows, beta, omb);
   }
 }
 
@@ -315,37 +301,7 @@ __global__ void __launch_bounds__(AF_THREADS) came_rmean_kernel(const float* __r
   if (threadIdx.x == 0) scratch[T.rmean_off + b] = t / (float)T.rows;
 }
 
-// ---- 4: sum u^2 per slab ----------------------------------------------------------------------------------------
-template <typename TG, bool BFROUND>
-__global__ void __launch_bounds__(AF_THREADS) came_unorm_kernel(const TG* __restrict__ Gr,
-                                                                const float* __restrict__ state,
-                                                                const float* __restrict__ scratch,
-                                                                double* __restrict__ slab_sq,
-                                                                const AdafactorTensor* __restrict__ tensors,
-                                                                const AdafactorSlab* __restrict__ slabs, int s0,
-                                                                const float* __restrict__ clip_coef) {
-  __shared__ float s_r[AF_STAGE];
-  __shared__ float s_c[AF_STAGE];
-  __shared__ double s_red[4];
-  const int si = s0 + blockIdx.x;
-  const AdafactorSlab sl = slabs[si];
-  const AdafactorTensor T = tensors[sl.tensor];
-  const bool clip = clip_coef != nullptr;
-  const float coef = clip ? clip_coef[0] : 1.f;
-  double acc = 0.0;
-  af_walk<TG, BFROUND>(Gr, state, scratch, T, sl, coef, clip, s_r, s_c,
-                       [&](long long, const float* g, const float* fac, unsigned valid) {
-                         float s = 0.f;
-#pragma unroll
-                         for (int j = 0; j < 8; ++j) {
-                           const float u = fac[j] * g[j];
-                           if (valid >> j & 1) s = fmaf(u, u, s);
-                         }
-                         acc += (double)s;
-                       });
-  const double t = af_block_sum_d(acc, s_red);
-  if (threadIdx.x == 0) slab_sq[si] = t;
-}
+// ---- 4: sum u^2 per slab: af_unorm_kernel<CameGroup, ...> (adafactor_walk.h) -> slab_sq[s] ----------------------
 
 // ---- 5: per-tensor scalars: the slab sums in slab order -> scal[t] = rms(u) ------------------------------------
 __global__ void came_scalars_kernel(const double* __restrict__ slab_sq, float* __restrict__ scal,
@@ -390,37 +346,9 @@ __global__ void __launch_bounds__(AF_THREADS) came_apply_kernel(TP* __restrict__
         if constexpr (FORM == 0)
           if (!sr) x = rbf(x);
       }
-      x = x - u;                 // p.add_(-update)
-      if constexpr (FORM == 0) {
-        if (sr) {
-          const uint32_t bits = (__float_as_uint(x) + sr_bits(k, (uint64_t)(v + j))) & 0xFFFF0000u;
-          x = __uint_as_float(bits);
-        } else {
-          x = rbf(x);
-        }
-      }
-      p[j] = x;
+      p[j] = x - u;              // p.add_(-update)
     }
-    if (valid == 0xFFu) {
-      if constexpr (FORM == 0) {
-        *reinterpret_cast<bf8*>(P + v) = pack8(p);
-      } else {
-        *reinterpret_cast<float4*>(P + v) = make_float4(p[0], p[1], p[2], p[3]);
-        *reinterpret_cast<float4*>(P + v + 4) = make_float4(p[4], p[5], p[6], p[7]);
-        if constexpr (FORM == 2) *reinterpret_cast<bf8*>(W + v) = pack8(p);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (valid >> j & 1) {
-          if constexpr (FORM == 0) {
-            reinterpret_cast<bf16_t*>(P)[v + j] = f2bf(p[j]);
-          } else {
-            reinterpret_cast<float*>(P)[v + j] = p[j];
-            if constexpr (FORM == 2) W[v + j] = f2bf(p[j]);
-          }
-        }
-    }
+    af_write_params<FORM>(P, W, v, p, valid, sr, k);
   };
   if (T.mode == 0) {   // update = exp_avg
     const long long e0 = T.offset + sl.row0, e1 = T.offset + sl.row1;
@@ -477,8 +405,8 @@ static int came_launch(const CameArgs& a, const CameGroups& G, hipStream_t strea
     came_rmean_kernel<<<nr, AF_THREADS, 0, stream>>>(a.state_sq, a.scratch_sq, a.tensors, a.fold, a.r0);
     OTAMD_CHECK_LAUNCH();
   }
-  came_unorm_kernel<TG, FORM == 0><<<ns, AF_THREADS, 0, stream>>>(g, a.state_sq, a.scratch_sq, a.slab_sq, a.tensors, a.slabs,
-                                                                  a.s0, a.clip_coef);
+  af_unorm_kernel<CameGroup, TG, FORM == 0><<<ns, AF_THREADS, 0, stream>>>(g, a.state_sq, a.scratch_sq, a.slab_sq, 1, 0,
+                                                                           a.tensors, a.slabs, a.s0, a.clip_coef);
   OTAMD_CHECK_LAUNCH();
   came_scalars_kernel<<<(nt + 255) / 256, 256, 0, stream>>>(a.slab_sq, a.scal, a.tensors, a.t0, a.t1);
   OTAMD_CHECK_LAUNCH();

@@ -876,29 +876,39 @@ def adamw_master(p32, g, m32, v32, w, groups, clip_coef=None, begin=0, end=None)
           "otamd_adamw_master_range")
 
 
+def _factored_step_checks(who, p, g, w, flat_f32, f32, slab_sq, sq_per_slab, scal, scal_per_tensor, tensors_dev,
+                          t_range, slabs_dev, s_range, groups) -> int:
+    """the argument checks adafactor_step and came_step share; returns the form (0 bf16 store, 1 fp32 store, 2 fp32
+    master + bf16 working copy w).  flat_f32: further fp32 buffers indexed as the store; f32: fp32 state buffers."""
+    n = p.numel()
+    _req(p.dtype in (BF16, F32) and g.dtype in (BF16, F32), f"{who} flat buffers: bf16 or fp32")
+    if w is not None:
+        form = 2
+        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, f"{who} master: fp32 p, bf16 g and w")
+    else:
+        form = 0 if p.dtype == BF16 else 1
+        _req(g.dtype == p.dtype, f"{who}: gradients in the store's dtype")
+    for t in (p, g) + tuple(flat_f32) + ((w,) if w is not None else ()):
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), f"{who} flat buffers")
+    for t in tuple(flat_f32) + tuple(f32) + (scal,):
+        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), f"{who} fp32 buffers")
+    nt, ns = tensors_dev.numel() // C.sizeof(_lib.AdafactorTensor), slabs_dev.numel() // C.sizeof(_lib.AdafactorSlab)
+    _req(slab_sq.is_cuda and slab_sq.dtype == torch.float64 and slab_sq.numel() >= sq_per_slab * ns,
+         f"{who} slab_sq f64[{sq_per_slab} * slabs]")
+    _req(scal.numel() >= scal_per_tensor * nt, f"{who} scal f32[{scal_per_tensor} * tensors]")
+    _req(0 <= t_range[0] <= t_range[1] <= nt and 0 <= s_range[0] <= s_range[1] <= ns, f"{who} table ranges")
+    _req(1 <= len(groups) <= 8, f"{who}: 1..8 parameter groups")
+    return form
+
+
 def adafactor_step(p, g, w, state, scratch, slab_sq, scal, tensors_dev, t_range, slabs_dev, s_range, groups,
                    clip_coef=None, stochastic_rounding=False, seed=0):
     """one fused Adafactor step (csrc/adafactor.hip) over the tensors t_range and slabs s_range of the device tables.
     p / g: the flat store and its gradients (bf16 / bf16, fp32 / fp32, or the fp32 master with bf16 gradients and
     the bf16 working copy w).  The tables name element ranges of these buffers: the caller built and checked them
     (util/optimizer/adafactor_fused.py)."""
-    n = p.numel()
-    _req(p.dtype in (BF16, F32) and g.dtype in (BF16, F32), "adafactor flat buffers: bf16 or fp32")
-    if w is not None:
-        form = 2
-        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, "adafactor master: fp32 p, bf16 g and w")
-    else:
-        form = 0 if p.dtype == BF16 else 1
-        _req(g.dtype == p.dtype, "adafactor: gradients in the store's dtype")
-    for t in (p, g) + ((w,) if w is not None else ()):
-        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "adafactor flat buffers")
-    for t in (state, scratch, scal):
-        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), "adafactor fp32 buffers")
-    _req(slab_sq.is_cuda and slab_sq.dtype == torch.float64 and slab_sq.numel() * 16 >= slabs_dev.numel(), "slab_sq f64")
-    _req(scal.numel() * C.sizeof(_lib.AdafactorTensor) >= 4 * tensors_dev.numel(), "scal f32[4 * tensors]")
-    nt, ns = tensors_dev.numel() // C.sizeof(_lib.AdafactorTensor), slabs_dev.numel() // C.sizeof(_lib.AdafactorSlab)
-    _req(0 <= t_range[0] <= t_range[1] <= nt and 0 <= s_range[0] <= s_range[1] <= ns, "adafactor table ranges")
-    _req(1 <= len(groups) <= 8, "adafactor: 1..8 parameter groups")
+    form = _factored_step_checks("adafactor", p, g, w, (), (state, scratch), slab_sq, 2, scal, 4, tensors_dev, t_range,
+                                 slabs_dev, s_range, groups)
     arr = (_lib.AdafactorGroup * len(groups))(*groups)
     check(lib().otamd_adafactor_step(_p(p), _p(g), _p(w), form, _p(state), _p(scratch), _p(slab_sq), _p(scal),
                                      _p(tensors_dev), t_range[0], t_range[1], _p(slabs_dev), s_range[0], s_range[1],
@@ -914,27 +924,12 @@ def came_step(p, g, w, m, state_sq, state_res, scratch_sq, scratch_res, slab_sq,
     store; state_sq / state_res and scratch_sq / scratch_res: the second-moment and instability states and their
     partials, pairwise of one size.  The tables name element ranges of these buffers: the caller built and checked
     them (util/optimizer/came_fused.py)."""
-    n = p.numel()
-    _req(p.dtype in (BF16, F32) and g.dtype in (BF16, F32), "came flat buffers: bf16 or fp32")
-    if w is not None:
-        form = 2
-        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, "came master: fp32 p, bf16 g and w")
-    else:
-        form = 0 if p.dtype == BF16 else 1
-        _req(g.dtype == p.dtype, "came: gradients in the store's dtype")
-    for t in (p, g, m) + ((w,) if w is not None else ()):
-        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "came flat buffers")
-    for t in (m, state_sq, state_res, scratch_sq, scratch_res, scal):
-        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), "came fp32 buffers")
+    form = _factored_step_checks("came", p, g, w, (m,), (state_sq, state_res, scratch_sq, scratch_res), slab_sq, 1,
+                                 scal, 1, tensors_dev, t_range, slabs_dev, s_range, groups)
     _req(state_sq.numel() == state_res.numel() and scratch_sq.numel() == scratch_res.numel(),
          "came: the instability buffers have the sizes of the second-moment buffers")
-    nt, ns = tensors_dev.numel() // C.sizeof(_lib.AdafactorTensor), slabs_dev.numel() // C.sizeof(_lib.AdafactorSlab)
     nf = fold_dev.numel() // C.sizeof(_lib.CameFold)
-    _req(slab_sq.is_cuda and slab_sq.dtype == torch.float64 and slab_sq.numel() >= ns, "slab_sq f64[slabs]")
-    _req(scal.numel() >= nt, "scal f32[tensors]")
-    _req(0 <= t_range[0] <= t_range[1] <= nt and 0 <= s_range[0] <= s_range[1] <= ns, "came table ranges")
     _req(0 <= f_range[0] <= f_range[1] <= nf and 0 <= r_range[0] <= r_range[1] <= nf, "came fold table ranges")
-    _req(1 <= len(groups) <= 8, "came: 1..8 parameter groups")
     arr = (_lib.CameGroup * len(groups))(*groups)
     check(lib().otamd_came_step(_p(p), _p(g), _p(w), form, _p(m), _p(state_sq), _p(state_res), _p(scratch_sq),
                                 _p(scratch_res), _p(slab_sq), _p(scal), _p(tensors_dev), t_range[0], t_range[1],

@@ -7,8 +7,8 @@ Same optimizer contract as FusedAdafactor (param_groups with 'lr', 'betas', 'eps
 'weight_decay'; step, zero_grad, clip_grad_norm_, step_parameter; state_dict / load_state_dict in the reference's
 layout: per parameter 'step', 'RMS', 'exp_avg' and 'exp_avg_sq_row' + 'exp_avg_sq_col' + 'exp_avg_res_row' +
 'exp_avg_res_col' or 'exp_avg_sq'; 'sr_seed' at the top level).  A step is nine launches over the whole store
-(csrc/came.hip) driven by the Adafactor tensor and slab tables (adafactor_fused.adafactor_tables) and a fold table
-built once here.
+(csrc/came.hip) driven by the Adafactor tensor and slab tables (factored_store.adafactor_tables) and a fold table
+built once here; the optimizer around them is factored_store.FactoredStoreOptimizer, shared with FusedAdafactor.
 
 States are fp32 whatever the parameter dtype, as the reference allocates them from the float gradient
 (CAME.py:84-109): the first moment is full-size, the second moment and the instability keep one row vector and one
@@ -32,8 +32,7 @@ import torch
 
 from ... import _lib
 from ... import kernels as K
-from .adafactor_fused import _to_device, adafactor_tables
-from .adamw_fused import FlatStoreOptimizer
+from .factored_store import FactoredStoreOptimizer, _to_device
 
 FOLD_BLOCK = 256   # csrc/came.hip: AF_THREADS rows, or columns, per fold workgroup (a thread each)
 
@@ -90,36 +89,24 @@ def _check_hyper(lr, betas):
         raise ValueError(f"CAME betas: three coefficients in [0, 1] are required, got {betas!r}")
 
 
-class FusedCAME(FlatStoreOptimizer):
+class FusedCAME(FactoredStoreOptimizer):
+    TUPLE_KEYS = ("eps", "betas")
+
     def __init__(self, store, param_groups, lr=None, eps=(1e-30, 1e-16), clip_threshold=1.0,
                  betas=(0.9, 0.999, 0.9999), weight_decay=0.0, stochastic_rounding=False, seed=0):
         _check_hyper(lr, betas)
         defaults = dict(lr=lr, eps=tuple(eps), clip_threshold=clip_threshold, betas=tuple(betas),
                         weight_decay=weight_decay)
         super().__init__(param_groups, defaults)
-        if len(self.param_groups) > 8:
-            raise ValueError("FusedCAME: at most 8 parameter groups")
         for g in self.param_groups:
             _check_hyper(g["lr"], g["betas"])
-        self._init_store(store)
-        self.stochastic_rounding = bool(stochastic_rounding)
-        self.seed = seed
-        self.steps = [0 for _ in self.param_groups]
-        entries = []
-        for gi, g in enumerate(self.param_groups):
-            for p in g["params"]:
-                s = store.slots[self._ptr2name[p.data_ptr()]]
-                entries.append((s.offset, s.shape, gi, s.name))
-        entries.sort(key=lambda e: e[0])
-        tensors, slabs, self._nt, self._ns, n_state, n_scratch = adafactor_tables([e[:3] for e in entries],
-                                                                                 store.numel)
+        self._init_factored(store, stochastic_rounding, seed)
+
+    def _alloc(self, tensors, n_state, n_scratch):
+        dev = self.store.device
         fold, self._nf, self._nm, self._fold_ranges = came_fold_table(tensors, self._nt)
-        self._table = [tensors[i] for i in range(self._nt)]          # host copies (state_dict, step_parameter)
-        names = [e[3] for e in entries if store.slots[e[3]].numel > 0]
-        self._tindex = {n: i for i, n in enumerate(names)}
-        dev = store.device
-        self._tensors, self._slabs, self._fold = _to_device(tensors, dev), _to_device(slabs, dev), _to_device(fold, dev)
-        self.exp_avg = torch.zeros(store.numel, dtype=torch.float32, device=dev)     # first moment, store layout
+        self._fold = _to_device(fold, dev)
+        self.exp_avg = torch.zeros(self.store.numel, dtype=torch.float32, device=dev)   # first moment, store layout
         self.state_buf = torch.zeros(n_state, dtype=torch.float32, device=dev)       # row / column / full second moments
         self.res_buf = torch.zeros(n_state, dtype=torch.float32, device=dev)         # row / column instability
         self._scratch = torch.zeros(n_scratch, dtype=torch.float32, device=dev)
@@ -127,7 +114,7 @@ class FusedCAME(FlatStoreOptimizer):
         self._slab_sq = torch.zeros(max(1, self._ns), dtype=torch.float64, device=dev)
         self._scal = torch.zeros(max(8, self._nt), dtype=torch.float32, device=dev)   # rms(u) per tensor
 
-    def _groups_struct(self):
+    def _groups_struct(self, steps=None):
         arr = []
         for g in self.param_groups:
             lr = float(g["lr"])
@@ -143,41 +130,19 @@ class FusedCAME(FlatStoreOptimizer):
             arr.append(s)
         return arr
 
-    def _launch(self, t_range, s_range, f_range, r_range, clip):
-        st = self.store
-        p = self.master if self.master is not None else st.data
-        w = st.data if self.master is not None else None
-        K.came_step(p, st.grad, w, self.exp_avg, self.state_buf, self.res_buf, self._scratch, self._scratch_res,
-                    self._slab_sq, self._scal, self._tensors, t_range, self._slabs, s_range, self._fold, f_range,
-                    r_range, self._groups_struct(), clip_coef=clip,
-                    stochastic_rounding=self.stochastic_rounding and w is None and st.dtype == torch.bfloat16,
-                    seed=self.seed)
+    def _ranges_all(self):
+        return super()._ranges_all() + ((0, self._nf), (self._nf, self._nf + self._nm))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        self.store.wait_params()
-        for gi in range(len(self.param_groups)):
-            self.steps[gi] += 1
-        clip = self.clip_out if self._pending_clip else None
-        self._pending_clip = False
-        if self.master is None and self.store.dtype == torch.bfloat16:
-            self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
-        self._launch((0, self._nt), (0, self._ns), (0, self._nf), (self._nf, self._nf + self._nm), clip)
-        return loss
-
-    def step_parameter(self, p, group, i):
-        """fused-back-pass API (CAME.py:79-178): update one parameter tensor."""
-        self.store.wait_params()
-        name = self._ptr2name[p.data_ptr()]
-        if name not in self._tindex:
-            return
-        ti = self._tindex[name]
-        t = self._table[ti]
+    def _ranges_of(self, ti):
         f0, f1, r0, r1 = self._fold_ranges[ti]
-        self._launch((ti, ti + 1), (t.slab0, t.slab0 + t.n_slabs), (f0, f1), (r0, r1), None)
+        return super()._ranges_of(ti) + ((f0, f1), (r0, r1))
 
-    # --- the reference's CAME state layout --------------------------------------------------------------------------
+    def _launch(self, p, g, w, groups, ranges, clip, sr):
+        K.came_step(p, g, w, self.exp_avg, self.state_buf, self.res_buf, self._scratch, self._scratch_res,
+                    self._slab_sq, self._scal, self._tensors, ranges[0], self._slabs, ranges[1], self._fold, ranges[2],
+                    ranges[3], groups, clip_coef=clip, stochastic_rounding=sr, seed=self.seed)
+
+    # --- the reference's CAME state layout (CAME.py:79-178) ---------------------------------------------------------
     def _views(self, name):
         """{state key: view of its buffer} of one tensor's moments"""
         s = self.store.slots[name]
@@ -190,38 +155,3 @@ class FusedCAME(FlatStoreOptimizer):
             v[f"exp_avg_{key}_row"] = buf[t.row_off:t.row_off + t.batch * t.rows].view(s.shape[:-1])
             v[f"exp_avg_{key}_col"] = buf[t.col_off:t.col_off + t.batch * t.cols].view(s.shape[:-2] + s.shape[-1:])
         return v
-
-    def state_dict(self):
-        self.store.wait_params()
-        state, groups, idx = {}, [], 0
-        for gi, g in enumerate(self.param_groups):
-            ids = []
-            for p in g["params"]:
-                name = self._ptr2name[p.data_ptr()]
-                if name in self._tindex:
-                    d = {"step": self.steps[gi], "RMS": torch.zeros(())}
-                    d.update({k: v.clone() for k, v in self._views(name).items()})
-                    state[idx] = d
-                ids.append(idx)
-                idx += 1
-            gd = {k: v for k, v in g.items() if k != "params"}
-            gd["params"] = ids
-            groups.append(gd)
-        # the stochastic-rounding stream position, so that a resumed run rounds like an uninterrupted one
-        return {"state": state, "param_groups": groups, "sr_seed": int(self.seed)}
-
-    def load_state_dict(self, sd):
-        self.store.wait_params()
-        if "sr_seed" in sd:
-            self.seed = int(sd["sr_seed"])
-        for gi, (g, gsd) in enumerate(zip(self.param_groups, sd["param_groups"])):
-            for k, v in gsd.items():
-                if k != "params":
-                    g[k] = tuple(v) if k in ("eps", "betas") else v
-            for p, pid in zip(g["params"], gsd["params"]):
-                name = self._ptr2name[p.data_ptr()]
-                st = sd["state"].get(pid)
-                if st and name in self._tindex:
-                    for k, v in self._views(name).items():
-                        v.copy_(st[k].reshape(v.shape))
-                    self.steps[gi] = int(float(st["step"]))

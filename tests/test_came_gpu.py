@@ -223,6 +223,57 @@ def test_state_dict_resumes_bit_exactly(dev, form, sr):
     assert _same_moments(oa, ob)
 
 
+def _rms_u(g, row, col):
+    """rms(u) in float64 on the host: u = g rsqrt(row / mean(row)) rsqrt(col) with the fresh states"""
+    g, row, col = (t.detach().double().cpu() for t in (g, row, col))
+    u = g * (row / row.mean(-1, keepdim=True)).rsqrt().unsqueeze(-1) * col.rsqrt().unsqueeze(-2)
+    return float(u.pow(2).mean().sqrt())
+
+
+@pytest.mark.parametrize("form", ["bf16", "f32"])
+def test_batched_big_matrices_step_as_separate_matrices(dev, form):
+    """mode 2 with batch 2: a (2, 70, 70) tensor (4900 elements a matrix: more than one LDS stage, and the second
+    matrix starts off the 8-element alignment) steps bit for bit as two (70, 70) tensors with the same values.  Row
+    sums depend on the column index within the tile only, column sums and row-state means on the row order only;
+    neither depends on alignment.  clip_threshold=100 keeps the per-tensor rms(u) clip inactive (checked on the
+    host): rms(u) is the one per-tensor quantity that differs between the two layouts."""
+    dtype = torch.float32 if form == "f32" else torch.bfloat16
+    cfg = dict(lr=LRS[0], clip_threshold=100.0)
+    a = FlatParamStore([("ab", (2, 70, 70), "a")], dtype, dev)
+    b = FlatParamStore([("m0", (70, 70), "a"), ("m1", (70, 70), "a")], dtype, dev)
+    p0 = AF.param0("ab", (2, 70, 70))
+    a.write("ab", torch.from_numpy(p0))
+    for i in range(2):
+        b.write(f"m{i}", torch.from_numpy(p0[i]))
+    oa = FusedCAME(a, [{"params": [a.params["ab"]]}], **cfg)
+    ob = FusedCAME(b, [{"params": [b.params["m0"], b.params["m1"]]}], **cfg)
+    assert oa._table[0].mode == 2 and oa._table[0].batch == 2 and a.slots["ab"].offset % 8 == 0
+    for k in range(AF.STEPS):
+        g = AF.grad("ab", (2, 70, 70), k)
+        a.params["ab"].grad.copy_(torch.from_numpy(g))
+        for i in range(2):
+            b.params[f"m{i}"].grad.copy_(torch.from_numpy(g[i]))
+        oa.step()
+        ob.step()
+        torch.cuda.synchronize()
+        va = oa._views("ab")
+        # rms(u) / clip_threshold < 1, recomputed on the host: the clip is inactive in both layouts
+        rms = [_rms_u(a.params["ab"].grad, va["exp_avg_sq_row"], va["exp_avg_sq_col"])]
+        rms += [_rms_u(b.params[f"m{i}"].grad, *(ob._views(f"m{i}")[key] for key in ("exp_avg_sq_row", "exp_avg_sq_col")))
+                for i in range(2)]
+        assert all(0 < r / cfg["clip_threshold"] < 1 for r in rms), rms
+        for i in range(2):
+            vb = ob._views(f"m{i}")
+            assert set(va) == set(vb) == {"exp_avg", "exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_res_row",
+                                          "exp_avg_res_col"}
+            for key in va:
+                assert torch.equal(va[key][i].view(torch.int32), vb[key].view(torch.int32)), (k, i, key)
+                assert va[key][i].abs().max() > 0
+            assert torch.equal(a.params["ab"][i].detach().view(torch.uint8),
+                               b.params[f"m{i}"].detach().view(torch.uint8)), (k, i)
+    assert not torch.equal(a.params["ab"].detach().float().cpu(), torch.from_numpy(p0))   # the steps moved it
+
+
 def _trainer_run(dev, method, overlap=True, steps=3):
     from onetrainer_amd.dataLoader.SyntheticDataLoader import synthetic_sdxl_batch
     from onetrainer_amd.module import unet as U

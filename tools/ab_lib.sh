@@ -1,5 +1,6 @@
 # Build the HIP library from the csrc/ of another git revision as onetrainer_amd/_lib/libotamd_<name>.so
 # (selected at run time with OTAMD_LIB_ALT=<name>; A/B of kernel changes inside one GPU call).
+# The per-file compiler flags are those of the current tree's build.py, whatever revision the sources come from.
 # usage: bash tools/ab_lib.sh <git-rev | WT> <name>
 set -e
 REV=$1; NAME=$2
@@ -12,11 +13,12 @@ else
 fi
 mkdir -p "$W/obj"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+# the per-file flags of the real build, one table: EXTRA of this tree's onetrainer_amd/build.py (not of $REV)
+FLAGS=$(cd "$ROOT" && python -c "from onetrainer_amd.build import EXTRA; [print(k, *v) for k, v in EXTRA.items()]")
 pids=()
 for f in "$W"/onetrainer_amd/csrc/*.hip; do
   b=$(basename "$f" .hip)
-  extra=""
-  case "$b" in adamw|diffusion) extra="-ffp-contract=off";; attention) extra="-fno-honor-nans -fno-slp-vectorize";; esac
+  extra=$(echo "$FLAGS" | sed -n "s/^$b.hip //p")
   "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -I "$W/onetrainer_amd/csrc" -c "$f" -o "$W/obj/$b.o" $extra &
   pids+=($!)
 done

@@ -2,11 +2,12 @@
 (2,567,486,728 elements) in one process: HIP events around step(), 3 warm-up + 10 timed steps, p50 (min - max), and
 the optimizer state each constructor allocates (torch.cuda.memory_allocated around it).  One JSON line per optimizer.
 
-usage: python tools/optimizer_step_time.py [--only ADAFACTOR,CAME] [--steps 10] [--warmup 3]
+usage: python tools/optimizer_step_time.py [--only ADAFACTOR,CAME] [--steps 10] [--warmup 3] [--digest]
 A kernel-trace run (rocprofv3 --kernel-trace --stats -- python tools/optimizer_step_time.py --only ADAFACTOR,CAME
 --warmup 1 --steps 3) gives the per-kernel split of both in one trace.
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -31,6 +32,14 @@ def build(name, store, params):
     return FusedCAME(store, groups, lr=1e-5, stochastic_rounding=True)
 
 
+def sha256(t, chunk=1 << 28):
+    h = hashlib.sha256()
+    flat = t.detach().view(-1).view(torch.uint8)
+    for i in range(0, flat.numel(), chunk):
+        h.update(flat[i:i + chunk].cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
 def moved_bytes(name, opt, n):
     """bytes one step reads and writes: per parameter (bf16 store) plus the factored states and partials"""
     if name == "ADAMW":
@@ -46,6 +55,8 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--digest", action="store_true", help="after the timed steps, a sha256 of the store and of each "
+                    "state buffer per optimizer")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model = U.UNet2DConditionModel(U.sdxl_config(), dev, seed=None)
@@ -78,6 +89,13 @@ def main():
                           "ms_p50": round(p50, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
                           "GB_step": round(nbytes / 1e9, 2), "TB_s": round(nbytes / p50 / 1e9, 3),
                           "state_GB": round(state_bytes / 1e9, 3)}), flush=True)
+        if a.digest:   # compare outputs at the size that is timed (two library builds: equal digests)
+            bufs = {"store.data": store.data}
+            bufs.update({k: v for k, v in sorted(vars(opt).items())
+                         if k in ("exp_avg", "exp_avg_sq", "state_buf", "res_buf")})
+            torch.cuda.synchronize()
+            for k, v in bufs.items():
+                print(json.dumps({"optimizer": name, "buffer": k, "sha256": sha256(v)}), flush=True)
         del opt
         torch.cuda.empty_cache()
 
