@@ -453,6 +453,15 @@ int otamd_noise_stream(void* out, int f32, long long n, long long offset, unsign
 int otamd_timesteps(int* out, int n, long long sample0, unsigned long long seed, int dist, int
     num_train_timesteps, int min_t, int max_t, float shift, float bias, float weight, const float* draws,
     hipStream_t s);
+/* the same with HEAVY_TAIL (dist 2, :107-118; weight = noising_weight) and the table samplers COS_MAP / SIGMOID
+   (dist 3, :119-153); dist 0 / 1 are passed on to otamd_timesteps.  All draw from the uniform of dist 0 (same Philox
+   stream and counter sample0 + i, or draws[i]).  dist 3: cdf = device fp32 [n_cdf], n_cdf = max_t - min_t > 0,
+   non-decreasing, last entry exactly 1.0 (util/timestep_table.timestep_cdf); out = min_t + the first index with
+   cdf[index] > u (strict: a zero-weight bucket is never returned); no shift after the draw.  cdf is not read for
+   dist 2. */
+int otamd_timesteps_ex(int* out, int n, long long sample0, unsigned long long seed, int dist, int
+    num_train_timesteps, int min_t, int max_t, float shift, float bias, float weight, const float* draws,
+    const float* cdf, int n_cdf, hipStream_t s);
 
 /* replaces: BaseStableDiffusionXLSetup.predict scale + _add_noise_discrete + get_velocity (BaseStableDiffusionXLSetup.py:214-236,277-291; ModelSetupDiffusionMixin.py:15-38) */
 int otamd_ddpm_prologue(const void* latent, const void* noise, int lat_f32, const int* timestep, const float*

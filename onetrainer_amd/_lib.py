@@ -231,6 +231,7 @@ SIGNATURES: dict[str, list] = {
     "otamd_noise_ex": [VP, I, LL, LL, U64, I, LL, F, F, VP],
     "otamd_noise_stream": [VP, I, LL, LL, U64, I, VP],
     "otamd_timesteps": [VP, I, LL, U64, I, I, I, I, F, F, F, VP, VP],
+    "otamd_timesteps_ex": [VP, I, LL, U64, I, I, I, I, F, F, F, VP, VP, I, VP],
     "otamd_ddpm_prologue": [VP, VP, I, VP, VP, VP, VP, F, I, LL, I, I, VP, VP, I, VP, VP],
     "otamd_flow_prologue": [VP, VP, I, VP, F, F, I, I, LL, I, I, VP, VP, VP],
     "otamd_mse_loss": [VP, I, VP, I, I, LL, I, F, F, VP, VP, VP, VP, I, F, I, I, F, VP, LL, VP, VP, VP, VP],

@@ -95,6 +95,16 @@ __global__ void noise_stream_kernel(void* out, int f32, long long n, long long o
     st_t(out, i, f32, round_t(philox_normal(seed, stream, (uint64_t)(offset + i)), f32));
 }
 
+// the shift map of the continuous samplers (ModelSetupNoiseMixin.py:118):
+// num_train_timesteps * shift * t / ((shift - 1) * t + num_train_timesteps): python scalars enter the
+// fp32 tensor ops as fp32 (N * shift is a python product, rounded once)
+__device__ __forceinline__ float shift_map(float t, int num_train_timesteps, float shift) {
+  const float N = (float)num_train_timesteps;
+  const float Ns = (float)((double)num_train_timesteps * (double)shift);
+  const float sm1 = (float)((double)shift - 1.0);
+  return (Ns * t) / (sm1 * t + N);
+}
+
 // timesteps for samples [sample0, sample0+n) of the global batch
 // dist 0 = UNIFORM, 1 = LOGIT_NORMAL (ModelSetupNoiseMixin.py:91-118).  draws != nullptr injects the
 // random draw of each sample instead of Philox (parity tests): UNIFORM -> the U[0,1) sample of
@@ -115,13 +125,41 @@ __global__ void timestep_kernel(int* out, int n, long long sample0, unsigned lon
     const float lg = 1.f / (1.f + expf(-nrm));
     t = lg * (float)(mx - mn) + (float)mn;
   }
-  // num_train_timesteps * shift * t / ((shift - 1) * t + num_train_timesteps): python scalars enter the
-  // fp32 tensor ops as fp32 (N * shift is a python product, rounded once)
-  const float N = (float)num_train_timesteps;
-  const float Ns = (float)((double)num_train_timesteps * (double)shift);
-  const float sm1 = (float)((double)shift - 1.0);
-  t = (Ns * t) / (sm1 * t + N);
-  out[i] = (int)t;   // .int() truncation
+  out[i] = (int)shift_map(t, num_train_timesteps, shift);   // .int() truncation
+}
+
+// dist 2 = HEAVY_TAIL (ModelSetupNoiseMixin.py:107-118), 3 = a table (COS_MAP / SIGMOID, :119-153), from the
+// uniform of dist 0: Philox stream 2 at counter sample0 + i, or draws[i].
+//   HEAVY_TAIL: u' = 1.0 - u - weight * (cos(pi/2 * u) ** 2.0 - 1.0 + u) in the reference's fp32 op order (pi/2 a
+//   python float rounded to fp32, ** 2.0 a product), t = u' * (mx - mn) + mn, the shift map, truncation.  A
+//   noising_weight that drives u' out of [0, 1] indexes past the scheduler's tables in the reference; here the
+//   result is held inside [0, num_train_timesteps - 1], which changes nothing for u' inside [0, 1].
+//   table: cdf[n_cdf] (n_cdf = mx - mn) non-decreasing fp32, last entry exactly 1.0; out = mn + the first index
+//   with cdf[index] > u, by binary search.  The comparison is strict, so a bucket with cdf[k] == cdf[k-1] (weight 0)
+//   is never returned.  u is held below 1.0 (an injected 1.0, or the rounding corner of u01), so cdf[n_cdf - 1] > u
+//   always holds and the search stays inside the table for any input.
+__global__ void timestep_ex_kernel(int* out, int n, long long sample0, unsigned long long seed, int dist,
+                                   int num_train_timesteps, int mn, int mx, float shift, float weight,
+                                   const float* draws, const float* cdf, int n_cdf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float u = draws ? draws[i] : philox_uniform(seed, 2u, (uint64_t)(sample0 + i));
+  if (dist == 2) {
+    const float c = cosf(1.5707963267948966f * u);
+    const float g = ((c * c) - 1.f) + u;
+    const float v = (1.f - u) - weight * g;
+    float t = shift_map(v * (float)(mx - mn) + (float)mn, num_train_timesteps, shift);
+    t = fminf(fmaxf(t, 0.f), (float)(num_train_timesteps - 1));
+    out[i] = (int)t;   // .int() truncation
+    return;
+  }
+  const float uc = fminf(u, 0.99999994f);   // the largest fp32 below 1
+  int lo = 0, hi = n_cdf - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cdf[mid] > uc) hi = mid; else lo = mid + 1;
+  }
+  out[i] = mn + lo;
 }
 
 // DDPM: scaled = latent*sf (latent dtype); x_t = scaled.f32*sqrt_acp[t] + noise.f32*sqrt_1m[t] -> latent dtype
@@ -428,6 +466,22 @@ OTAMD_API int otamd_timesteps(int* out, int n, long long sample0, unsigned long 
     return OTAMD_EINVAL;
   timestep_kernel<<<(n + 63) / 64, 64, 0, s>>>(out, n, sample0, seed, dist, num_train_timesteps, min_t, max_t, shift,
                                                bias, weight, draws);
+  OTAMD_CHECK_LAUNCH();
+  return OTAMD_OK;
+}
+// dist 0 / 1: otamd_timesteps; 2 = HEAVY_TAIL; 3 = table (cdf: device fp32 [n_cdf], n_cdf = max_t - min_t)
+OTAMD_API int otamd_timesteps_ex(int* out, int n, long long sample0, unsigned long long seed, int dist,
+                                 int num_train_timesteps, int min_t, int max_t, float shift, float bias, float weight,
+                                 const float* draws, const float* cdf, int n_cdf, hipStream_t s) {
+  if (dist == 0 || dist == 1)
+    return otamd_timesteps(out, n, sample0, seed, dist, num_train_timesteps, min_t, max_t, shift, bias, weight, draws,
+                           s);
+  if (!out || n <= 0 || num_train_timesteps <= 0 || (dist != 2 && dist != 3) || min_t < 0 || max_t < min_t ||
+      max_t > num_train_timesteps)
+    return OTAMD_EINVAL;
+  if (dist == 3 && (!cdf || n_cdf <= 0 || n_cdf != max_t - min_t)) return OTAMD_EINVAL;
+  timestep_ex_kernel<<<(n + 63) / 64, 64, 0, s>>>(out, n, sample0, seed, dist, num_train_timesteps, min_t, max_t,
+                                                  shift, weight, draws, cdf, n_cdf);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

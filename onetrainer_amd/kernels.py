@@ -1546,8 +1546,10 @@ def noise_stream(n, seed, stream_id, offset=0, dtype=F32, device=None):
 
 
 def timesteps(n, seed, sample0=0, dist=0, num_train_timesteps=1000, min_s=0.0, max_s=1.0, shift=1.0, bias=0.0,
-              weight=0.0, device=None, out=None, draws=None):
-    """draws: optional f32 [n] injected draws (U[0,1) for UNIFORM, the N(bias, weight+1) sample for LOGIT_NORMAL)."""
+              weight=0.0, device=None, out=None, draws=None, cdf=None):
+    """dist: the ids of TIMESTEP_DIST (0 UNIFORM, 1 LOGIT_NORMAL, 2 HEAVY_TAIL, 3 COS_MAP, 4 SIGMOID).
+    draws: optional f32 [n] injected draws (the N(bias, weight+1) sample for LOGIT_NORMAL, U[0,1) for the others).
+    cdf: ids 3 and 4 only, the f32 [max_t - min_t] table of util/timestep_table.timestep_cdf on the output's device."""
     if out is None:
         out = torch.empty(n, dtype=torch.int32, device=device)
     _req(out.numel() == n and out.dtype == torch.int32 and out.is_contiguous(), "timesteps out")
@@ -1555,9 +1557,21 @@ def timesteps(n, seed, sample0=0, dist=0, num_train_timesteps=1000, min_s=0.0, m
         _req(draws.dtype == F32 and draws.numel() == n and draws.is_contiguous() and draws.device == out.device,
              "timestep draws: f32 [n] on the output's device")
     mn, mx = int(num_train_timesteps * min_s), int(num_train_timesteps * max_s)   # python ints, like :69-70
-    check(lib().otamd_timesteps(_p(out), n, sample0, seed & 0xFFFFFFFFFFFFFFFF, dist, num_train_timesteps, mn, mx,
-                                float(shift), float(bias), float(weight), _p(draws), stream_handle()),
-          "otamd_timesteps")
+    if dist in (0, 1):
+        _req(cdf is None, "timestep cdf: only the table distributions (ids 3, 4) take one")
+        check(lib().otamd_timesteps(_p(out), n, sample0, seed & 0xFFFFFFFFFFFFFFFF, dist, num_train_timesteps, mn, mx,
+                                    float(shift), float(bias), float(weight), _p(draws), stream_handle()),
+              "otamd_timesteps")
+        return out
+    _req(dist in (2, 3, 4), f"timestep distribution id {dist}")
+    if dist == 2:
+        _req(cdf is None, "timestep cdf: only the table distributions (ids 3, 4) take one")
+    else:
+        _req(cdf is not None and cdf.dtype == F32 and cdf.is_contiguous() and cdf.device == out.device
+             and cdf.numel() == mx - mn, "timestep cdf: f32 [max_t - min_t] on the output's device")
+    check(lib().otamd_timesteps_ex(_p(out), n, sample0, seed & 0xFFFFFFFFFFFFFFFF, min(dist, 3), num_train_timesteps,
+                                   mn, mx, float(shift), float(bias), float(weight), _p(draws), _p(cdf),
+                                   0 if cdf is None else cdf.numel(), stream_handle()), "otamd_timesteps_ex")
     return out
 
 

@@ -1,7 +1,7 @@
 """predict / calculate_loss for FLUX.1 on the HIP kernels.
 
 Drop-in for modules/modelSetup/BaseFluxSetup.py:193-390 with the math of ModelSetupNoiseMixin
-(noise; LOGIT_NORMAL / UNIFORM timesteps, static or dynamic shift), ModelSetupFlowMatchingMixin.py:14-39
+(noise; timesteps of all five distributions, static or dynamic shift), ModelSetupFlowMatchingMixin.py:14-39
 (sigma = (t + 1) / N, x_t = sigma noise + (1 - sigma) x0), FluxModel.pack/unpack_latents and
 ModelSetupDiffusionLossMixin._flow_matching_losses (MSE, or masked / MAE / log-cosh; flow target noise - x0):
   * latents arrive [B, 16, h, w] (this build's loaders: a view of channels-last storage);
@@ -20,9 +20,10 @@ import torch
 from .. import kernels as K
 from ..module import flux_ops as O
 from ..module import functional as Fn
-from .BaseStableDiffusionXLSetup import (draw_noise, loss_mask, loss_plan, nhwc_pair, plain_mse, report_learning_rates,
-                                         timestep_plan)
+from .BaseStableDiffusionXLSetup import (draw_noise, draw_timesteps, loss_mask, loss_plan, nhwc_pair, plain_mse,
+                                         report_learning_rates)
 from ..util.config.plain import plain
+from ..util.timestep_table import TimestepTables
 
 
 class BaseFluxSetup:
@@ -33,6 +34,7 @@ class BaseFluxSetup:
         self.dp_rank = dp_rank
         self.dp_world = dp_world
         self.graph_inputs = None   # injected (noise NHWC, timestep int32): parity tests
+        self.timestep_tables = TimestepTables()   # COS_MAP / SIGMOID cumulative tables on the device
 
     @staticmethod
     def _nhwc_latent(lat: torch.Tensor) -> torch.Tensor:
@@ -66,6 +68,23 @@ class BaseFluxSetup:
         mu = (w // 2) * (h // 2) * m + (0.5 - m * 256)
         return math.exp(mu)
 
+    def step_inputs(self, model, batch: dict, config, train_progress, *, deterministic: bool = False):
+        """(noise NHWC, timestep int32) of this micro-step (ModelSetupNoiseMixin._create_noise /
+        _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index."""
+        config = plain(config)
+        batch_seed = 0 if deterministic else train_progress.global_step
+        latent = batch["latent_image"]
+        B, C, h, w = latent.shape
+        N = model.noise_scheduler.config["num_train_timesteps"]
+        sample0 = self.dp_rank * B
+        noise = draw_noise(config, (B, h, w, C), batch_seed, sample0 * h * w * C, latent.dtype, latent.device)
+        if deterministic:
+            timestep = torch.full((B,), int(N * 0.5) - 1, dtype=torch.int32, device=latent.device)
+        else:
+            timestep = draw_timesteps(self.timestep_tables, config, B, batch_seed, sample0, N,
+                                      self._shift(config, h, w), latent.device)
+        return noise, timestep
+
     def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False) -> dict:
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
@@ -77,15 +96,7 @@ class BaseFluxSetup:
         if self.graph_inputs is not None:
             noise, timestep = self.graph_inputs
         else:
-            sample0 = self.dp_rank * B
-            noise = draw_noise(config, latent.shape, batch_seed, sample0 * h * w * C, latent.dtype, latent.device)
-            if deterministic:
-                timestep = torch.full((B,), int(N * 0.5) - 1, dtype=torch.int32, device=latent.device)
-            else:
-                timestep = K.timesteps(B, seed=batch_seed, sample0=sample0, dist=timestep_plan(config),
-                                       num_train_timesteps=N, min_s=config.min_noising_strength, max_s=config.max_noising_strength,
-                                       shift=self._shift(config, h, w), bias=config.noising_bias,
-                                       weight=config.noising_weight, device=latent.device)
+            noise, timestep = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic)
         vc = model.vae.config
         model_in, target = K.flow_prologue(latent, noise, timestep, vc["scaling_factor"], vc["shift_factor"], N,
                                            cpad=C)

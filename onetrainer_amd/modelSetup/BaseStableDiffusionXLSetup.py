@@ -22,9 +22,10 @@ import torch
 from .. import kernels as K
 from ..module import functional as Fn
 from ..util.config.plain import plain
+from ..util.timestep_table import TABLE_DISTS, TimestepTables
 
 LOSS_FN = {"CONSTANT": 0, "MIN_SNR_GAMMA": 1, "DEBIASED_ESTIMATION": 2, "P2": 3}
-TIMESTEP_DIST = {"UNIFORM": 0, "LOGIT_NORMAL": 1}
+TIMESTEP_DIST = {"UNIFORM": 0, "LOGIT_NORMAL": 1, "HEAVY_TAIL": 2, "COS_MAP": 3, "SIGMOID": 4}
 
 
 def loss_plan(config, flow: bool = False) -> dict:
@@ -77,12 +78,27 @@ def loss_mask(batch: dict, plan: dict, device):
 
 
 def timestep_plan(config) -> int:
-    """kernel id of config.timestep_distribution (ModelSetupNoiseMixin.py:91-118); the discrete
-    SIGMOID / COS_MAP / HEAVY_TAIL samplers are outside C1-C5."""
+    """kernel id of config.timestep_distribution (ModelSetupNoiseMixin.py:91-153): the continuous UNIFORM /
+    LOGIT_NORMAL / HEAVY_TAIL and the table-driven COS_MAP / SIGMOID (util/timestep_table.py)."""
     d = config.timestep_distribution
     if d not in TIMESTEP_DIST:
         raise NotImplementedError(f"timestep distribution {d} is not on this build's hot path")
     return TIMESTEP_DIST[d]
+
+
+def draw_timesteps(tables: TimestepTables, config, B, seed, sample0, N, shift, device, out=None):
+    """_get_timestep_discrete (ModelSetupNoiseMixin.py:69-155, not deterministic) for samples [sample0, sample0 + B)
+    of the global batch; `shift` as the setup resolved it.  COS_MAP / SIGMOID read their cumulative table from
+    `tables` (built and uploaded on first use of an argument set, outside any capture)."""
+    dist = timestep_plan(config)
+    cdf = None
+    if config.timestep_distribution in TABLE_DISTS:
+        cdf = tables.cdf(config.timestep_distribution, N, int(N * config.min_noising_strength),
+                         int(N * config.max_noising_strength), shift, config.noising_bias, config.noising_weight,
+                         device)
+    return K.timesteps(B, seed=seed, sample0=sample0, dist=dist, num_train_timesteps=N,
+                       min_s=config.min_noising_strength, max_s=config.max_noising_strength, shift=shift,
+                       bias=config.noising_bias, weight=config.noising_weight, device=device, out=out, cdf=cdf)
 
 
 def draw_noise(config, shape, seed, offset, dtype, device, out=None):
@@ -134,6 +150,7 @@ class BaseStableDiffusionXLSetup:
         self.dp_rank = dp_rank
         self.dp_world = dp_world
         self.graph_inputs = None   # (noise, timestep) drawn outside a captured step (trainer/step_graph.py)
+        self.timestep_tables = TimestepTables()   # COS_MAP / SIGMOID cumulative tables on the device
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
@@ -188,11 +205,8 @@ class BaseStableDiffusionXLSetup:
             if out is not None:
                 timestep = out[1].copy_(timestep)
         else:
-            timestep = K.timesteps(B, seed=batch_seed, sample0=sample0, dist=timestep_plan(config), num_train_timesteps=N,
-                                   min_s=config.min_noising_strength, max_s=config.max_noising_strength,
-                                   shift=config.timestep_shift, bias=config.noising_bias,
-                                   weight=config.noising_weight, device=lat.device,
-                                   out=None if out is None else out[1])
+            timestep = draw_timesteps(self.timestep_tables, config, B, batch_seed, sample0, N, config.timestep_shift,
+                                      lat.device, out=None if out is None else out[1])
         return noise, timestep
 
     def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False) -> dict:
