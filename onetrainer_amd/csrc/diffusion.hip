@@ -118,14 +118,19 @@ __global__ void timestep_kernel(int* out, int n, long long sample0, unsigned lon
   if (i >= n) return;
   float t;
   if (dist == 0) {
-    const float u = draws ? draws[i] : philox_uniform(seed, 2u, (uint64_t)(sample0 + i));
-    t = (float)mn + (float)(mx - mn) * u;
+    // the Philox uniform is held below 1.0 (the rounding corner of u01: 0xFFFFFF + 0.5 rounds to 2^24), as
+    // timestep_ex_kernel holds it: torch.rand is in [0, 1), and u = 1 is timestep max_t, one past the tables
+    const float u = draws ? draws[i] : fminf(philox_uniform(seed, 2u, (uint64_t)(sample0 + i)), 0.99999994f);
+    t = shift_map((float)mn + (float)(mx - mn) * u, num_train_timesteps, shift);
   } else {
     const float nrm = draws ? draws[i] : bias + (weight + 1.f) * philox_normal(seed, 3u, (uint64_t)(sample0 + i));
     const float lg = 1.f / (1.f + expf(-nrm));
-    t = lg * (float)(mx - mn) + (float)mn;
+    // the sigmoid is exactly 1.0 from nrm ~ 17.4 on (max_t again): the result is held inside
+    // [0, num_train_timesteps - 1] like HEAVY_TAIL's, which changes nothing for a result inside
+    t = shift_map(lg * (float)(mx - mn) + (float)mn, num_train_timesteps, shift);
+    t = fminf(fmaxf(t, 0.f), (float)(num_train_timesteps - 1));
   }
-  out[i] = (int)shift_map(t, num_train_timesteps, shift);   // .int() truncation
+  out[i] = (int)t;   // .int() truncation
 }
 
 // dist 2 = HEAVY_TAIL (ModelSetupNoiseMixin.py:107-118), 3 = a table (COS_MAP / SIGMOID, :119-153), from the

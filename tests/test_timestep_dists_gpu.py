@@ -47,7 +47,10 @@ def picked_uniforms(cdf):
 def philox_uniforms(dev, n, seed, sample0=0):
     """the uniforms of samples [sample0, sample0 + n), recovered exactly from UNIFORM at N = 2^24 over the whole range
     with shift 1: there t0 = 2^24 u and the shift map (2^24 t0) / (0 t0 + 2^24) are exact, u = (k + 0.5) / 2^24 with
-    k < 2^24 truncates to k below 2^23, and from 2^23 on k + 0.5 is rounded to the integer t itself"""
+    k < 2^24 truncates to k below 2^23, and from 2^23 on k + 0.5 is rounded to the integer t itself (ties to even: k
+    or k + 1).  k = 0xFFFFFF is the exception: its k + 0.5 rounds to 2^24, u01 is exactly 1.0, and every timestep
+    kernel holds that uniform at the largest fp32 below 1, so t = 2^24 - 1 and what is returned is that held value,
+    the u the kernels use"""
     t = K.timesteps(n, seed=seed, sample0=sample0, dist=0, num_train_timesteps=1 << 24, device=dev).cpu().numpy()
     return (np.where(t < (1 << 23), t + 0.5, t.astype(np.float64)) / 2.0 ** 24).astype(np.float32)
 
