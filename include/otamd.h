@@ -385,6 +385,16 @@ int otamd_lora_shadow(const float* src, void* dst, const void* table, int n_entr
 /* replaces: ABI check */
 int otamd_lora_shadow_entry_size(void);
 
+/* replaces: the dropout of LoRAModule.forward (modules/module/LoRAModule.py:319-323, lora_up(dropout(lora_down(x))))
+   in place on t = lora_down(x) (bf16 [M, width], contiguous), and on u = dy (sB) in the backward with the same mask.
+   One Philox4x32-10 call per row and group of 4 columns: Wq = ceil(width / 4), call index q = site_id * 2^40 +
+   (row0 + m) * Wq + quad, counter (lo32(q), hi32(q), 6, 0x64726f70), key = *seed (device memory: a captured step
+   draws a new mask on every replay); word k belongs to column 4 quad + k.  Kept iff (uint64)word >= thr, thr =
+   floor(p * 2^32) in [0, 2^32]; kept -> bf16_rne(float(t) * scale), dropped -> +0.  row0 = the row of the global
+   (all ranks) tensor that row 0 of t is.  site_id in [0, 2^24), (row0 + M) * Wq <= 2^40. */
+int otamd_lora_dropout(void* t, long long M, int width, const unsigned long long* seed, int site_id, long long row0,
+    unsigned long long thr, float scale, hipStream_t s);
+
 /* replaces: DoRAModule.forward's weight expression (modules/module/LoRAModule.py:385-412) for every adapted module in
    one launch: n = ||W + s up down|| over every axis but the kept one (axis 0: input channels, 1: output channels)
    + eps, written to `norms`, and W' = bf16(dora_scale * ((W + s up down) / n)) written to `wp` (0 where n == 0).

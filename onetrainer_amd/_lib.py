@@ -198,6 +198,8 @@ SIGNATURES: dict[str, list] = {
     "otamd_cast_f32": [VP, VP, LL, I, I, VP],
     "otamd_lora_shadow": [VP, VP, VP, I, VP],
     "otamd_lora_shadow_entry_size": [],
+    # lora_dropout.hip
+    "otamd_lora_dropout": [VP, LL, I, VP, I, LL, U64, F, VP],
     # dora.hip
     "otamd_dora_merge": [VP, VP, I, I, F, VP, LL, VP, LL, VP, LL, VP, LL, VP],
     "otamd_dora_project": [VP, VP, I, I, I, I, VP, LL, VP, VP, LL, VP, LL, VP, LL, I, VP],

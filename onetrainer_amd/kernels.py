@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import math
 import os
 
 import torch
@@ -1433,6 +1434,35 @@ def lora_shadow(src_f32: torch.Tensor, dst_bf16: torch.Tensor, table: torch.Tens
     _req(src_f32.dtype == F32 and dst_bf16.dtype == BF16 and table.dtype == torch.uint8, "lora shadow dtypes")
     check(lib().otamd_lora_shadow(_p(src_f32), _p(dst_bf16), _p(table), n_entries, stream_handle()),
           "otamd_lora_shadow")
+
+
+def lora_dropout_consts(p: float) -> tuple:
+    """(thr, scale) of a dropout rate: thr = floor(p * 2^32) in double (an element is kept iff its 32-bit Philox word
+    >= thr), scale = 1 / (1 - p), rounded to fp32 at the call (inf at p = 1, where nothing is kept)."""
+    _req(isinstance(p, (int, float)) and 0.0 <= p <= 1.0, f"dropout rate {p!r} outside [0, 1]")
+    p = float(p)
+    return int(math.floor(p * 4294967296.0)), (1.0 / (1.0 - p) if p < 1.0 else math.inf)
+
+
+def lora_dropout(t: torch.Tensor, seed_dev: torch.Tensor, site_id: int, row0: int, p: float) -> torch.Tensor:
+    """LoRA dropout in place on t = lora_down(x) (or u = dy (sB) in the backward): bf16, contiguous, [M, width] over
+    its last dimension (LoRAModule.forward, modules/module/LoRAModule.py:319-323).  The mask is Philox4x32-10 stream 6
+    at (site_id, row0 + m, column), keyed by the 64-bit seed in the one-element int64 device tensor seed_dev (read by
+    the kernel at run time); row0 = the global row of t's first row (csrc/lora_dropout.hip).  Returns t."""
+    _req(t.dtype == BF16 and t.is_cuda and t.dim() >= 2 and t.is_contiguous() and t.data_ptr() % 2 == 0,
+         "lora_dropout: contiguous bf16 cuda [M, width]")
+    _req(seed_dev.dtype == torch.int64 and seed_dev.numel() == 1 and seed_dev.device == t.device
+         and seed_dev.data_ptr() % 8 == 0, "lora_dropout: seed is a one-element int64 tensor on t's device")
+    width = t.shape[-1]
+    _req(width > 0, "lora_dropout: empty rows")
+    M = t.numel() // width
+    Wq = (width + 3) // 4
+    _req(0 <= site_id < (1 << 24), "lora_dropout: site_id outside [0, 2^24)")
+    _req(row0 >= 0 and (row0 + M) * Wq <= (1 << 40), "lora_dropout: (row0 + M) * ceil(width / 4) above 2^40")
+    thr, scale = lora_dropout_consts(p)
+    check(lib().otamd_lora_dropout(_p(t), M, width, _p(seed_dev), site_id, row0, thr, scale, stream_handle()),
+          "otamd_lora_dropout")
+    return t
 
 
 def _dora_args(base, params, norms, buf):

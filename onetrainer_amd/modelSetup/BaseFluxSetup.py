@@ -73,6 +73,9 @@ class BaseFluxSetup:
         _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index."""
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
+        lora = getattr(model, "transformer_lora", None)
+        if getattr(lora, "dropout_p", 0) > 0:   # LoRA dropout masks: the same seed as the noise
+            lora.set_dropout_seed(batch_seed)
         latent = batch["latent_image"]
         B, C, h, w = latent.shape
         N = model.noise_scheduler.config["num_train_timesteps"]

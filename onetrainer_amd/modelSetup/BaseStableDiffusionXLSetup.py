@@ -192,6 +192,9 @@ class BaseStableDiffusionXLSetup:
         _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index."""
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
+        lora = getattr(model, "unet_lora", None)
+        if getattr(lora, "dropout_p", 0) > 0:   # LoRA dropout masks: the same seed, written outside a captured step
+            lora.set_dropout_seed(batch_seed)
         lat = batch["latent_image"]
         B = lat.shape[0]
         shape = tuple(self._nhwc_latent(lat).shape) if out is None else tuple(out[0].shape)

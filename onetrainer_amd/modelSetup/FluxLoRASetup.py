@@ -40,12 +40,18 @@ class FluxLoRASetup(BaseFluxSetup):
         model.dtype_plan = dtype_plan(config)   # util/dtype_util.py: the config's dtypes honoured, overridden or refused
         model.train_dtype = torch.bfloat16
 
-    def setup_model(self, model, config):
+    @staticmethod
+    def check_options(config) -> float:
+        """refuse the adapter options this build does not run (DoRA / LoHa) and return the LoRA dropout rate; needs
+        no model"""
         config = plain(config)
         if getattr(config, "lora_decompose", False) or config.peft_type != "LORA":
             raise NotImplementedError("DoRA / LoHa are not on this build's hot path")
-        if config.dropout_probability and config.dropout_probability > 0:
-            raise NotImplementedError("LoRA dropout > 0 is not on this build's hot path")
+        return float(config.dropout_probability or 0.0)
+
+    def setup_model(self, model, config):
+        config = plain(config)
+        dropout = self.check_options(config)
         if model.transformer.store.trainable:
             raise ValueError("LoRA training needs a frozen base transformer (create_model(..., training_method='LORA'))")
         self.setup_optimizations(model, config)
@@ -57,6 +63,8 @@ class FluxLoRASetup(BaseFluxSetup):
             model.transformer_lora.load_state_dict(model.lora_state_dict)
             model.lora_state_dict = None
         model.transformer.lora = model.transformer_lora
+        model.transformer_lora.set_dropout(dropout)   # LoRAModuleWrapper.set_dropout (LoRAModule.py:580-587)
+        model.transformer_lora.dp_rank = self.dp_rank
         params = self.create_parameters(model, config)
         model.parameters = params
         model.optimizer = create_optimizer(model.transformer_lora.store, params.parameters_for_optimizer(config), config)

@@ -46,8 +46,9 @@ class StableDiffusionXLLoRASetup(BaseStableDiffusionXLSetup):
         if config.peft_type != "LORA":
             raise NotImplementedError("LoHa is not on this build's hot path")
         decompose = bool(getattr(config, "lora_decompose", False))
-        if config.dropout_probability and config.dropout_probability > 0:
-            raise NotImplementedError("LoRA dropout > 0 is not on this build's hot path")
+        dropout = float(config.dropout_probability or 0.0)
+        if decompose and dropout > 0:
+            raise NotImplementedError("DoRA with LoRA dropout > 0 is not on this build's hot path")
         if model.unet.store.trainable:
             raise ValueError("LoRA training needs a frozen base UNet (create_model(..., training_method='LORA'))")
         self.setup_optimizations(model, config)
@@ -64,9 +65,15 @@ class StableDiffusionXLLoRASetup(BaseStableDiffusionXLSetup):
             model.unet_lora.load_state_dict(model.lora_state_dict)
             model.lora_state_dict = None
         if isinstance(model.unet_lora, DoRAWrapper):
+            if dropout > 0:
+                raise NotImplementedError("DoRA with LoRA dropout > 0 is not on this build's hot path")
             model.unet.dora = model.unet_lora
         else:
             model.unet.lora = model.unet_lora
+            # LoRAModuleWrapper.set_dropout (LoRAModule.py:580-587); the masks are seeded per step (step_inputs) and
+            # each data-parallel rank draws its rows of the global batch's mask
+            model.unet_lora.set_dropout(dropout)
+            model.unet_lora.dp_rank = self.dp_rank
         params = self.create_parameters(model, config)
         model.parameters = params
         model.optimizer = create_optimizer(model.unet_lora.store, params.parameters_for_optimizer(config), config)

@@ -57,6 +57,9 @@ class RowsLinearFn(torch.autograd.Function):
             xs = x[r0:r1]
             if site is not None:
                 t = K.linear(xs, site.down)
+                drop = site.drop()
+                if drop is not None:   # LoRA dropout: each segment's t has its own row index starting at 0
+                    drop.dropout(t, site)
                 K.linear(xs, wref.w, bias=bref.w if bref is not None else None, lora=(t, site.up2), out=y[r0:r1])
                 ts.append(t)
             else:
@@ -76,6 +79,9 @@ class RowsLinearFn(torch.autograd.Function):
             dys, xs = dy[r0:r1], x[r0:r1]
             btr = bref is not None and bref.trainable
             u = K.linear_dgrad(dys, site.up2) if site is not None else None
+            drop = site.drop() if site is not None else None
+            if drop is not None:   # the forward's mask, drawn again, before both readers of u
+                drop.dropout(u, site)
             if site is not None or wref.trainable or btr:
                 with S.wgrad_region((dys, xs, t, u)):
                     if site is not None:

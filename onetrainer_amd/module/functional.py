@@ -178,7 +178,9 @@ class LoraLinearFn(torch.autograd.Function):
     modules/module/LoRAModule.py:318-322).  Forward: one launch with t = x A^T accumulated in the base GEMM's K loop
     and [t | s B] as its second K segment (kernels.linear_lora; two launches where the plan does not allow it).
     Backward: u = dy (sB); dx = [dy | u] [W ; A] (one GEMM; at r = 32 on single-module and q|k|v sites u is
-    accumulated inside it, kernels.linear_dgrad_lora); dA = u^T x; dB_p = s dy_p^T t_p per fused part; all adapter grads fp32."""
+    accumulated inside it, kernels.linear_dgrad_lora); dA = u^T x; dB_p = s dy_p^T t_p per fused part; all adapter grads fp32.
+    With LoRA dropout (site.drop()) t and u are masked in place between the launches (kernels.lora_dropout, the same
+    mask both times), so forward and input gradient take their two-launch forms."""
 
     @staticmethod
     def forward(ctx, x, wref, bref, residual, site, *params):
@@ -186,8 +188,16 @@ class LoraLinearFn(torch.autograd.Function):
         x2 = _rows(x)
         r2 = _rows(residual) if residual is not None else None
         t = torch.empty((x2.shape[0], site.down.shape[0]), dtype=x2.dtype, device=x2.device)
-        y = K.linear_lora(x2, wref.w, bref.w if bref is not None else None, r2, site.down, site.up2, t, site.rank,
-                          site.part_width)
+        drop = site.drop()
+        if drop is not None:
+            # LoRA dropout masks t between down and up, so the down projection cannot run inside the base GEMM: t,
+            # the mask (in place; the saved t is the dropped one), then the base GEMM with t as its second K segment
+            K.linear(x2, site.down, out=t)
+            drop.dropout(t, site)
+            y = K.linear(x2, wref.w, bias=bref.w if bref is not None else None, residual=r2, lora=(t, site.up2))
+        else:
+            y = K.linear_lora(x2, wref.w, bref.w if bref is not None else None, r2, site.down, site.up2, t, site.rank,
+                              site.part_width)
         ctx.save_for_backward(x2, t)
         ctx.wref, ctx.bref, ctx.site, ctx.has_res, ctx.xshape = wref, bref, site, residual is not None, shp
         return y.view(*shp[:-1], wref.w.shape[0])
@@ -198,6 +208,7 @@ class LoraLinearFn(torch.autograd.Function):
         wref, bref, site = ctx.wref, ctx.bref, ctx.site
         btr = bref is not None and bref.trainable
         need_dx = ctx.needs_input_grad[0]
+        drop = site.drop()
 
         def wgrads(dy2, u):
             acc = site.acc()
@@ -218,12 +229,15 @@ class LoraLinearFn(torch.autograd.Function):
                 dy2 = _rows(dy)
                 if dy2.stride(1) != 1 or dy2.stride(0) % 8:
                     dy2 = dy2.contiguous()
-                wgrads(dy2, K.linear_dgrad(dy2, site.up2))
+                u = K.linear_dgrad(dy2, site.up2)
+                if drop is not None:   # the forward's mask, drawn again; u is only a weight-gradient operand here
+                    drop.dropout(u, site)
+                wgrads(dy2, u)
         else:
             dy2 = _rows(dy)
             if dy2.stride(1) != 1 or dy2.stride(0) % 8:
                 dy2 = dy2.contiguous()
-            if need_dx and site.upT is not None:
+            if need_dx and site.upT is not None and drop is None:
                 # one launch: u = dy (sB) inside the input-gradient GEMM's K loop (kernels.linear_dgrad_lora)
                 u = torch.empty((dy2.shape[0], site.up2.shape[1]), dtype=dy2.dtype, device=dy2.device)
                 dx = K.linear_dgrad_lora(dy2, wref.w, site.up2, site.down, site.upT, site.downT, u).view(ctx.xshape)
@@ -231,6 +245,8 @@ class LoraLinearFn(torch.autograd.Function):
                     wgrads(dy2, u)
             else:
                 u = K.linear_dgrad(dy2, site.up2)
+                if drop is not None:   # the forward's mask, drawn again: on this stream, before both readers of u
+                    drop.dropout(u, site)
                 with S.wgrad_region((dy2, x2, t, u)):
                     wgrads(dy2, u)
                 if need_dx:
@@ -301,8 +317,15 @@ class LoraConvFn(torch.autograd.Function):
     def forward(ctx, x, wref, bref, rowvec, residual, stride, upsample, site, *params):
         Ho, Wo = K.conv_out_hw(x.shape[1], x.shape[2], site.k, stride, 1, upsample)
         t = torch.empty((x.shape[0], Ho, Wo, site.down.shape[0]), dtype=x.dtype, device=x.device)
-        y = K.conv2d_lora(x, wref.w, bref.w if bref is not None else None, stride, 1, upsample, residual, rowvec,
-                          site.down, site.up2, t, site.rank)
+        drop = site.drop()
+        if drop is not None:   # LoRA dropout: the two-launch form with the mask on t in between (LoraLinearFn)
+            K.conv2d(x, site.down, stride=stride, pad=1, upsample=upsample, out=t)
+            drop.dropout(t, site)
+            y = K.conv2d(x, wref.w, bias=bref.w if bref is not None else None, stride=stride, pad=1, upsample=upsample,
+                         residual=residual, rowvec=rowvec, lora=(t, site.up2))
+        else:
+            y = K.conv2d_lora(x, wref.w, bref.w if bref is not None else None, stride, 1, upsample, residual, rowvec,
+                              site.down, site.up2, t, site.rank)
         ctx.save_for_backward(x, t)
         ctx.wref, ctx.bref, ctx.stride, ctx.upsample, ctx.site = wref, bref, stride, upsample, site
         ctx.has_rowvec, ctx.has_res = rowvec is not None, residual is not None
@@ -321,6 +344,9 @@ class LoraConvFn(torch.autograd.Function):
         dy2 = dy.reshape(M, Cout)
         r = site.rank
         u = K.linear_dgrad(dy2, site.up2).view(N, P, Q, r)          # dy (s B)
+        drop = site.drop()
+        if drop is not None:   # the forward's mask, drawn again
+            drop.dropout(u, site)
         btr = bref is not None and bref.trainable
         with S.wgrad_region((dy, x, t, u)):
             acc = site.acc()

@@ -5,7 +5,9 @@ every Linear / Conv2d of the UNet whose name matches the layer filter gets
     y = orig(x) + up(down(x)) * (alpha / rank)
 with `down` a Linear in->r (Conv2d: the base kernel/stride/padding, in->r), `up` a Linear r->out
 (Conv2d: 1x1 r->out), down ~ kaiming_uniform(a=sqrt(5)) = U(+-1/sqrt(fan_in)), up = 0,
-dropout p = 0, adapter weights fp32 (TrainConfig lora_weight_dtype), computed in bf16.
+adapter weights fp32 (TrainConfig lora_weight_dtype), computed in bf16.  Dropout (set_dropout, default 0) masks
+down(x) before up: a Philox mask per (site, global row, column), keyed by the step's seed held in device memory and
+drawn again in the backward (csrc/lora_dropout.hip); the site then runs as two launches with the mask in between.
 Names / state-dict keys follow the reference: "lora_unet.<module>.lora_down.weight",
 ".lora_up.weight" (diffusers NCHW layouts for conv) and ".alpha".
 
@@ -63,6 +65,13 @@ class LoraSite:
     rank: int = 0
     params: tuple = ()
     group: tuple = ()        # all modules of the base GEMM (adapted or not)
+    site_id: int = 0         # index in wrapper.sites: the site's part of the dropout mask's Philox counter
+    wrapper: object = field(default=None, repr=False, compare=False)   # the LoRAWrapper (dropout rate / seed); DoRA: None
+
+    def drop(self):
+        """the wrapper when LoRA dropout is on (module/functional.py, module/flux_ops.py), else None"""
+        w = self.wrapper
+        return w if w is not None and w.dropout_p > 0 else None
 
     @property
     def part_width(self) -> int:
@@ -156,7 +165,13 @@ class LoRAWrapper:
         sites = discover_sites(model, rank, self.scale, module_filter)
         self.sites = sites
         self.site_of = {}
-        for s in sites:
+        self.dropout_p = 0.0   # LoRAModuleWrapper.set_dropout
+        self.dp_rank = 0       # data-parallel rank: rank r draws rows [r M, (r + 1) M) of the global mask
+        # the dropout seed (batch_seed of the step), read by the kernel from device memory so that a replayed step
+        # graph draws a new mask; written eagerly before every step (the setups' step_inputs)
+        self.drop_seed = torch.zeros(1, dtype=torch.int64, device=model.device)
+        for i, s in enumerate(sites):
+            s.site_id, s.wrapper = i, self
             for mname in s.group:
                 self.site_of[mname] = s
             self.site_of[s.key] = s
@@ -229,6 +244,26 @@ class LoRAWrapper:
         if s is not None and tuple(modules) != s.group:
             raise NotImplementedError(f"base GEMM {modules} does not match the LoRA fusion group {s.group}")
         return s
+
+    # ----- dropout -------------------------------------------------------------------------------
+    def set_dropout(self, dropout_probability: float):
+        """LoRAModuleWrapper.set_dropout (LoRAModule.py:580-587)"""
+        if dropout_probability < 0 or dropout_probability > 1:
+            raise ValueError("Dropout probability must be in [0, 1]")
+        if len(self.sites) > (1 << 24):
+            raise ValueError("LoRA dropout numbers at most 2^24 sites")
+        self.dropout_p = float(dropout_probability)
+
+    def set_dropout_seed(self, seed: int):
+        """the seed of the masks drawn from now on (an ordinary eager write, outside any captured step)"""
+        seed &= 0xFFFFFFFFFFFFFFFF
+        self.drop_seed.fill_(seed - (1 << 64) if seed >= (1 << 63) else seed)
+
+    def dropout(self, t: torch.Tensor, site: "LoraSite") -> torch.Tensor:
+        """mask t = down(x) (forward) or u = dy (sB) (backward) of `site` in place: t is [M, P r] over its last
+        dimension, its rows sample-major, row 0 being row dp_rank * M of the global batch's tensor"""
+        M = t.numel() // t.shape[-1]
+        return K.lora_dropout(t, self.drop_seed, site.site_id, self.dp_rank * M, self.dropout_p)
 
     # ----- parameters ----------------------------------------------------------------------------
     def init_weights(self, seed: int):
