@@ -127,6 +127,16 @@ typedef struct CameGroup {
 } CameGroup;
 typedef struct CameFold { long long i0, i1; int tensor, kind; } CameFold;
 
+/* Prodigy (csrc/prodigy.hip).  ProdigyState: the device-resident scalars of the step size, all fp64; the host writes
+   them at start-up and on load only.  dlr: d lr bc of the step in flight (from d before it); k: completed steps;
+   skip: 1 when the step in flight found d_denom == 0.  ProdigyHyper: the launch arguments, passed by pointer from
+   the host and by value to the kernels; beta3 resolved (sqrt(beta2) when the configuration leaves it open). */
+typedef struct ProdigyState { double d, d_max, d_numerator, d_denom, d_hat, dlr, k, skip; } ProdigyState;
+typedef struct ProdigyHyper {
+  double lr, beta1, beta2, beta3, eps, weight_decay, d0, d_coef, growth_rate;
+  int decouple, use_bias_correction, safeguard_warmup, pad;
+} ProdigyHyper;
+
 /* replaces: diffusers Linear/Conv2d fwd+bwd inside model.unet(...) (modules/modelSetup/BaseStableDiffusionXLSetup.py:268-273); conv/linear dgrad/wgrad of loss.backward() (modules/trainer/GenericTrainer.py:693-696) */
 int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long long ws_bytes, hipStream_t stream);
 
@@ -593,6 +603,41 @@ int otamd_came_step(void* p, const void* g, void* w16, int form, float* m, float
 int otamd_came_group_size(void);
 /* replaces: ABI check */
 int otamd_came_fold_size(void);
+
+/* replaces: the state pass of prodigyopt.Prodigy.step as modules/util/create.py:863-881 builds it (the package is
+   not in the reference tree: the contract is the published step, restated in tests/_oracle_prodigy.py).  One
+   workgroup per NormChunk of the grad-norm chunk table (8-aligned begin, at most 65536 elements, inside one tensor;
+   the caller checked the ranges): with g the gradient after the pending clip (clip_coef, nullable; bf16-rounded in
+   form 0) plus weight_decay p in the coupled form, and d, k read from `state`: num += g (p0 - p) (fp32 difference,
+   fp64 product and sum), m = beta1 m + d (1 - beta1) g (beta1 > 0; m may be null otherwise), v = beta2 v +
+   d^2 (1 - beta2) g g, s = beta3 s + a g with a = (d / d0) dlr or (d / d0) d under safeguard_warmup, den += |s|;
+   chunk_num[c], chunk_den[c]: one fp64 slot per chunk, no atomics.  p0 / m / v / s: fp32, indexed as the store.
+   form 0: p, g bf16; 1: p, g fp32; 2: p the fp32 master, g bf16.  capture_p0: the first step, p0 = p is written
+   instead of read.  One launch. */
+int otamd_prodigy_accumulate(const void* p, const void* g, int form, float* p0, float* m, float* v, float* s,
+    const void* chunks, int n_chunks, double* chunk_num, double* chunk_den, const void* state,
+    const ProdigyHyper* hyper, const float* clip_coef, int capture_p0, hipStream_t stream);
+
+/* replaces: the scalar part of Prodigy.step: one workgroup folds the chunk slots in a fixed order and updates
+   `state` (device ProdigyState) in fp64: d_numerator = beta3 d_numerator + (d / d0) dlr num, d_denom = den; den == 0
+   sets skip and changes nothing else; otherwise d_hat = d_coef d_numerator / d_denom, d = max(d, d_hat) while
+   d == d0, d_max = max(d_max, d_hat), d = min(d_max, d growth_rate), k += 1, skip = 0.  One launch. */
+int otamd_prodigy_finalize(const double* chunk_num, const double* chunk_den, int n_chunks, void* state,
+    const ProdigyHyper* hyper, hipStream_t stream);
+
+/* replaces: the parameter update of Prodigy.step over the n elements of the store (a multiple of 8), reading d, dlr
+   and skip from `state`: nothing when skip; else p += (-weight_decay dlr) p (decoupled form), p -= dlr m /
+   (sqrt(v) + d eps) with the new d and the step's dlr; beta1 == 0: d g stands for m (g, clip_coef as accumulate saw
+   them).  form as above; w16: the bf16 working copy of form 2, rewritten as rne(p); form 0 rounds to nearest or
+   stochastically (the AdamW dither on the element index).  Workgroup cap OTAMD_ADAMW_BLOCKS.  One launch. */
+int otamd_prodigy_apply(void* p, void* w16, const void* g, int form, const float* m, const float* v, long long n,
+    const void* state, const ProdigyHyper* hyper, const float* clip_coef, int stochastic_rounding,
+    unsigned long long seed, hipStream_t stream);
+
+/* replaces: ABI check */
+int otamd_prodigy_state_size(void);
+/* replaces: ABI check */
+int otamd_prodigy_hyper_size(void);
 
 /* replaces: EMAModuleWrapper.step (modules/module/EMAModule.py:37-54), ema.add_(one_minus_decay * (parameter - ema))
    per tensor, for elements [begin, end) of the flat buffers (multiples of 8, 16-byte aligned pointers; padding is 0

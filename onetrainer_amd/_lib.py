@@ -80,6 +80,16 @@ class CameFold(C.Structure):
     _fields_ = [("i0", C.c_longlong), ("i1", C.c_longlong), ("tensor", C.c_int), ("kind", C.c_int)]
 
 
+class ProdigyState(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("d", "d_max", "d_numerator", "d_denom", "d_hat", "dlr", "k", "skip")]
+
+
+class ProdigyHyper(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "beta3", "eps", "weight_decay", "d0", "d_coef",
+                                          "growth_rate")] + [
+        ("decouple", C.c_int), ("use_bias_correction", C.c_int), ("safeguard_warmup", C.c_int), ("pad", C.c_int)]
+
+
 class LoraShadowEntry(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("rows", C.c_int), ("cols", C.c_int),
                 ("dst_ld", C.c_int), ("scale", C.c_float), ("transpose", C.c_int), ("pad", C.c_int)]
@@ -153,6 +163,12 @@ SIGNATURES: dict[str, list] = {
                         C.POINTER(CameGroup), I, VP, I, C.c_ulonglong, VP],
     "otamd_came_group_size": [],
     "otamd_came_fold_size": [],
+    # prodigy.hip
+    "otamd_prodigy_accumulate": [VP, VP, I, VP, VP, VP, VP, VP, I, VP, VP, VP, C.POINTER(ProdigyHyper), VP, I, VP],
+    "otamd_prodigy_finalize": [VP, VP, I, VP, C.POINTER(ProdigyHyper), VP],
+    "otamd_prodigy_apply": [VP, VP, VP, I, VP, VP, LL, VP, C.POINTER(ProdigyHyper), VP, I, C.c_ulonglong, VP],
+    "otamd_prodigy_state_size": [],
+    "otamd_prodigy_hyper_size": [],
     # ema.hip
     "otamd_ema_range": [VP, VP, I, LL, LL, F, VP],
     "otamd_ema_sweep_elems": [I],
@@ -289,4 +305,6 @@ def check_layouts():
     assert L.otamd_adafactor_group_size() == C.sizeof(AdafactorGroup)
     assert L.otamd_came_group_size() == C.sizeof(CameGroup)
     assert L.otamd_came_fold_size() == C.sizeof(CameFold)
+    assert L.otamd_prodigy_state_size() == C.sizeof(ProdigyState)
+    assert L.otamd_prodigy_hyper_size() == C.sizeof(ProdigyHyper)
     assert L.otamd_dora_entry_size() == C.sizeof(DoraEntry)

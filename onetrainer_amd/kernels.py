@@ -940,6 +940,69 @@ def came_step(p, g, w, m, state_sq, state_res, scratch_sq, scratch_res, slab_sq,
           "otamd_came_step")
 
 
+def prodigy_form(p, g, w) -> int:
+    """the C-ABI form code of csrc/prodigy.hip: 0 bf16 store, 1 fp32 store, 2 fp32 master p with bf16 gradients and
+    the bf16 working copy w"""
+    if w is not None:
+        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, "prodigy master: fp32 p, bf16 g and w")
+        return 2
+    _req(p.dtype in (BF16, F32) and g.dtype == p.dtype, "prodigy: a bf16 or fp32 store with gradients in its dtype")
+    return 0 if p.dtype == BF16 else 1
+
+
+def _prodigy_flat(n, same, f32):
+    for t in same:
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "prodigy flat buffers")
+    for t in f32:
+        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == n and _aligned(t),
+             "prodigy fp32 states, indexed as the store")
+
+
+def _prodigy_state(state):
+    _req(state.is_cuda and state.dtype == torch.float64 and state.is_contiguous()
+         and state.numel() * 8 == C.sizeof(_lib.ProdigyState), "prodigy state block")
+
+
+def prodigy_accumulate(p, g, w, p0, m, v, s, chunks_dev, n_chunks, chunk_num, chunk_den, state, hyper, clip_coef=None,
+                       capture_p0=False):
+    """pass 1 of a fused Prodigy step (csrc/prodigy.hip): the states m (None when beta1 == 0), v, s and the two
+    per-chunk fp64 sums over the grad-norm chunk table, whose ranges the caller checked
+    (util/optimizer/prodigy_fused.py).  p / g / w as prodigy_form; state: the device ProdigyState (fp64[8])."""
+    form = prodigy_form(p, g, w)
+    _prodigy_flat(p.numel(), (p, g), (p0, v, s) + ((m,) if m is not None else ()))
+    _prodigy_state(state)
+    _req(m is not None or hyper.beta1 == 0.0, "prodigy: the first moment is required when beta1 > 0")
+    _req(0 <= n_chunks <= chunks_dev.numel() // C.sizeof(_lib.NormChunk), "prodigy chunk table")
+    for t in (chunk_num, chunk_den):
+        _req(t.is_cuda and t.dtype == torch.float64 and t.numel() >= n_chunks, "prodigy chunk sums f64[chunks]")
+    check(lib().otamd_prodigy_accumulate(_p(p), _p(g), form, _p(p0), _p(m), _p(v), _p(s), _p(chunks_dev), n_chunks,
+                                         _p(chunk_num), _p(chunk_den), _p(state), C.byref(hyper), _p(clip_coef),
+                                         int(capture_p0), stream_handle()),
+          "otamd_prodigy_accumulate")
+
+
+def prodigy_finalize(chunk_num, chunk_den, n_chunks, state, hyper):
+    """pass 2: fold the chunk sums and update the device scalars (d, d_max, d_numerator, k; dlr and skip for apply)"""
+    _prodigy_state(state)
+    for t in (chunk_num, chunk_den):
+        _req(t.is_cuda and t.dtype == torch.float64 and t.numel() >= n_chunks >= 0, "prodigy chunk sums f64[chunks]")
+    check(lib().otamd_prodigy_finalize(_p(chunk_num), _p(chunk_den), n_chunks, _p(state), C.byref(hyper),
+                                       stream_handle()),
+          "otamd_prodigy_finalize")
+
+
+def prodigy_apply(p, g, w, m, v, state, hyper, clip_coef=None, stochastic_rounding=False, seed=0):
+    """pass 3: the parameter update over the whole store with the new d the finalize left in `state`"""
+    form = prodigy_form(p, g, w)
+    _prodigy_flat(p.numel(), (p, g) + ((w,) if w is not None else ()), (v,) + ((m,) if m is not None else ()))
+    _prodigy_state(state)
+    _req(m is not None or hyper.beta1 == 0.0, "prodigy: the first moment is required when beta1 > 0")
+    check(lib().otamd_prodigy_apply(_p(p), _p(w), _p(g), form, _p(m), _p(v), p.numel(), _p(state), C.byref(hyper),
+                                    _p(clip_coef), int(stochastic_rounding), seed & 0xFFFFFFFFFFFFFFFF,
+                                    stream_handle()),
+          "otamd_prodigy_apply")
+
+
 def ema_form(ema, p) -> int:
     """the C-ABI form code of csrc/ema.hip: 0 bf16 shadow of bf16 parameters, 1 fp32 / fp32, 2 fp32 shadow of bf16
     parameters."""

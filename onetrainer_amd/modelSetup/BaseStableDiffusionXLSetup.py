@@ -113,15 +113,19 @@ def draw_noise(config, shape, seed, offset, dtype, device, out=None):
 
 def report_learning_rates(model, lr_scheduler, tensorboard):
     """BaseModelSetup.report_to_tensorboard (modules/modelSetup/BaseModelSetup.py:96-119): the scheduler's
-    last lr of each parameter group as `lr/<display name prefix>`, the first group of a prefix winning
-    (AdamW's maybe_adjust_lrs is the identity)."""
+    last lr of each parameter group as `lr/<display name prefix>`, the first group of a prefix winning.  An adaptive
+    optimizer's groups carry its step-size estimate `d`, and lr * d is reported, as Optimizer.maybe_adjust_lrs
+    (modules/util/enum/Optimizer.py:99-105) does; for the others (no `d`) it is the identity."""
     lrs = lr_scheduler.get_last_lr()
     names = model.parameters.display_name_mapping()
     if len(lrs) != len(names):
         raise ValueError(f"{len(lrs)} learning rates for {len(names)} parameter groups")
+    groups = getattr(getattr(model, "optimizer", None), "param_groups", None)
+    if groups is None or len(groups) != len(lrs):
+        groups = [{}] * len(lrs)
     reported = {}
-    for lr, name in zip(lrs, names):
-        reported.setdefault(name.split("/")[0], lr)
+    for lr, name, group in zip(lrs, names, groups):
+        reported.setdefault(name.split("/")[0], lr * group.get("d", 1.0))
     for name, lr in reported.items():
         tensorboard.add_scalar(f"lr/{name}", lr, model.train_progress.global_step)
 

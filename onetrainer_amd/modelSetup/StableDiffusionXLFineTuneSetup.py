@@ -1,5 +1,5 @@
 """Full fine-tune plugin (mirrors modules/modelSetup/StableDiffusionXLFineTuneSetup.py:26-164):
-parameter groups, optimizer creation (util/create.py create_optimizer: fused AdamW, Adafactor or CAME), device placement."""
+parameter groups, optimizer creation (util/create.py create_optimizer: fused AdamW, Adafactor, CAME or Prodigy), device placement."""
 from __future__ import annotations
 
 import torch

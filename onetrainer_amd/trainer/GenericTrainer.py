@@ -103,7 +103,7 @@ class GenericTrainer(TimedActionMixin):
         self._attach_norm_overlap()
 
     def _attach_norm_overlap(self):
-        """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor, CAME): clip_grad_norm_'s norm pass runs during backward
+        """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor, CAME, Prodigy): clip_grad_norm_'s norm pass runs during backward
         (util/optimizer/adamw_fused.OverlappedGradNorm) -- in one process as gradient ranges finish, under data
         parallel as the reducer's buckets finish their all-reduce (the norm of the global-mean gradients)."""
         import os

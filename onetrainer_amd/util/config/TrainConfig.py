@@ -28,6 +28,15 @@ class OptimizerConfig:
     warmup_init: bool | None = None
     # CAME (None resolves as modules/util/create.py:944-949 does)
     beta3: float | None = None
+    # PRODIGY (None resolves as modules/util/create.py:865-880 does; beta3 None means sqrt(beta2))
+    decouple: bool | None = None
+    use_bias_correction: bool | None = None
+    safeguard_warmup: bool | None = None
+    d0: float | None = None
+    d_coef: float | None = None
+    growth_rate: float | None = None
+    fsdp_in_use: bool | None = None
+    slice_p: int | None = None
     stochastic_rounding: bool = True
     fused_back_pass: bool = False
     foreach: bool | None = False

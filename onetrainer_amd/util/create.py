@@ -1,5 +1,5 @@
 """Factories (mirrors the parts of modules/util/create.py the hot path uses:
-create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
+create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 863-881 (PRODIGY), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
 1114-1232, create_noise_scheduler 1235-1373)."""
 from __future__ import annotations
 
@@ -124,9 +124,41 @@ def came_options(oc) -> dict:
                 beta3=pick("beta3", 0.9999), weight_decay=pick("weight_decay", 0))
 
 
+def prodigy_options(oc) -> dict:
+    """OptimizerConfig -> prodigyopt.Prodigy arguments, None resolved exactly as create.py:865-880 resolves it (beta3
+    stays None there: the optimizer takes sqrt(beta2))."""
+    def pick(name, default):
+        v = getattr(oc, name, None)
+        return v if v is not None else default
+    return dict(beta1=pick("beta1", 0.9), beta2=pick("beta2", 0.999), beta3=pick("beta3", None), eps=pick("eps", 1e-8),
+                weight_decay=pick("weight_decay", 0), decouple=pick("decouple", True),
+                use_bias_correction=pick("use_bias_correction", False),
+                safeguard_warmup=pick("safeguard_warmup", False), d0=pick("d0", 1e-6), d_coef=pick("d_coef", 1.0),
+                growth_rate=pick("growth_rate", float("inf")), fsdp_in_use=pick("fsdp_in_use", False),
+                slice_p=pick("slice_p", 1))
+
+
+def check_prodigy(o, oc, groups):
+    """what the fused Prodigy does not do, refused by the option's name before anything is allocated"""
+    if o["slice_p"] != 1:
+        raise NotImplementedError(f"PRODIGY slice_p={o['slice_p']}: only slice_p 1 (every element feeds the step-size "
+                                  "estimate) is on the hot path")
+    if o["fsdp_in_use"]:
+        raise NotImplementedError("PRODIGY fsdp_in_use: sharded parameters are not supported (data parallel keeps "
+                                  "whole, all-reduced gradients on every rank)")
+    if getattr(oc, "fused_back_pass", False):
+        raise NotImplementedError("PRODIGY fused_back_pass: the step needs sums over the whole store, so no "
+                                  "parameter can be updated during the backward pass")
+    lrs = sorted({float(g["lr"]) for g in groups if "lr" in g})
+    if len(lrs) > 1:
+        raise NotImplementedError(f"PRODIGY learning_rate: parameter groups with different learning rates {lrs} are "
+                                  "not supported (d is one estimate for the whole store)")
+
+
 def create_optimizer(store, groups, config):
     """the fused optimizer over `store` for config.optimizer (create.py:509-534 ADAMW + patch_adamw, 914-936
-    ADAFACTOR + patch_adafactor, 938-951 CAME).  Anything else is refused: there is no eager fall-back."""
+    ADAFACTOR + patch_adafactor, 938-951 CAME, 863-881 PRODIGY).  Anything else is refused: there is no eager
+    fall-back."""
     config = plain(config)
     oc = config.optimizer
     name = str(oc.optimizer)
@@ -155,7 +187,17 @@ def create_optimizer(store, groups, config):
         return FusedCAME(store, groups, lr=config.learning_rate, eps=(o["eps"], o["eps2"]),
                          betas=(o["beta1"], o["beta2"], o["beta3"]), weight_decay=o["weight_decay"],
                          stochastic_rounding=bool(oc.stochastic_rounding))
-    raise NotImplementedError(f"optimizer {name}: only ADAMW, ADAFACTOR and CAME are on the hot path")
+    if name == "PRODIGY":
+        o = prodigy_options(oc)
+        check_prodigy(o, oc, groups)
+        from .optimizer.prodigy_fused import FusedProdigy
+        return FusedProdigy(store, groups, lr=config.learning_rate, betas=(o["beta1"], o["beta2"]), beta3=o["beta3"],
+                            eps=o["eps"], weight_decay=o["weight_decay"], decouple=o["decouple"],
+                            use_bias_correction=o["use_bias_correction"], safeguard_warmup=o["safeguard_warmup"],
+                            d0=o["d0"], d_coef=o["d_coef"], growth_rate=o["growth_rate"],
+                            stochastic_rounding=bool(oc.stochastic_rounding))
+    raise NotImplementedError(f"optimizer {name}: only ADAMW, ADAFACTOR and CAME (with a learning rate of "
+                              "your choice) and PRODIGY (which estimates it) are on the hot path")
 
 
 def create_ema(store, state_dict, config):
