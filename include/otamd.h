@@ -137,6 +137,17 @@ typedef struct ProdigyHyper {
   int decouple, use_bias_correction, safeguard_warmup, pad;
 } ProdigyHyper;
 
+/* Schedule-free AdamW (csrc/schedule_free.hip).  SfGroup: one parameter group of a step, by value from the host:
+   element range [begin, end) (begin a multiple of 8), lr after the warm-up factor, a_y = lr (beta1 (1 - ckp1) - 1),
+   ckp1 = weight / weight_sum, beta2, 1 - beta2, 1 / bc2, eps, weight_decay; first: the group's first step (z = y is
+   taken from the parameters instead of read).  SfSwapGroup: one group of a mode switch, p += w (z - p). */
+typedef struct SfGroup {
+  long long begin, end;
+  float lr, a_y, ckp1, beta2, one_minus_beta2, inv_bc2, eps, weight_decay;
+  int first, pad;
+} SfGroup;
+typedef struct SfSwapGroup { long long begin, end; float w; int pad; } SfSwapGroup;
+
 /* replaces: diffusers Linear/Conv2d fwd+bwd inside model.unet(...) (modules/modelSetup/BaseStableDiffusionXLSetup.py:268-273); conv/linear dgrad/wgrad of loss.backward() (modules/trainer/GenericTrainer.py:693-696) */
 int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long long ws_bytes, hipStream_t stream);
 
@@ -638,6 +649,31 @@ int otamd_prodigy_apply(void* p, void* w16, const void* g, int form, const float
 int otamd_prodigy_state_size(void);
 /* replaces: ABI check */
 int otamd_prodigy_hyper_size(void);
+
+/* replaces: the non-foreach path of schedulefree.AdamWScheduleFree.step as modules/util/create.py:752-767 builds it
+   (the package is not in the reference tree: the contract is the step restated in tests/_oracle_schedule_free.py).
+   Over elements [begin, end) (multiples of 8) of a store of n elements, per group (at most 8, sorted, disjoint), with
+   g the gradient after the pending clip (clip_coef, nullable; bf16-rounded in form 0): v = beta2 v + (1 - beta2) g g,
+   gn = g / (sqrt(v inv_bc2) + eps) + weight_decay y, y = y + ckp1 (z - y), y = y + a_y gn, z = z - lr gn; every fp32
+   operation one rounding, no fused multiply-add.  z / v: fp32, indexed as the store; elements outside every group
+   (the store's padding) are not written.  form 0: p, g bf16, rounded to nearest or stochastically (the AdamW dither
+   on the element index); 1: p, g fp32; 2: p the fp32 master, g bf16, w16 the bf16 working copy rewritten as rne(p).
+   Workgroup cap OTAMD_ADAMW_BLOCKS.  One launch, no atomics. */
+int otamd_sf_adamw_step(void* p, void* w16, const void* g, int form, float* z, float* v, long long n, long long begin,
+    long long end, const SfGroup* groups, int n_groups, const float* clip_coef, int stochastic_rounding,
+    unsigned long long seed, hipStream_t stream);
+
+/* replaces: AdamWScheduleFree.eval() / .train() (p.lerp_(z, 1 - 1/beta1) / p.lerp_(z, 1 - beta1)), called by
+   modules/trainer/GenericTrainer.py:414-449, 470-483, 772-775 around every backup and save: p = p + w (z - p) over
+   the groups' ranges inside [begin, end).  Forms as above; form 0 always rounds to nearest (a mode switch is
+   repeatable).  One launch. */
+int otamd_sf_swap(void* p, void* w16, int form, const float* z, long long n, long long begin, long long end,
+    const SfSwapGroup* groups, int n_groups, hipStream_t stream);
+
+/* replaces: ABI check */
+int otamd_sf_group_size(void);
+/* replaces: ABI check */
+int otamd_sf_swap_group_size(void);
 
 /* replaces: EMAModuleWrapper.step (modules/module/EMAModule.py:37-54), ema.add_(one_minus_decay * (parameter - ema))
    per tensor, for elements [begin, end) of the flat buffers (multiples of 8, 16-byte aligned pointers; padding is 0

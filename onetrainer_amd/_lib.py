@@ -90,6 +90,16 @@ class ProdigyHyper(C.Structure):
         ("decouple", C.c_int), ("use_bias_correction", C.c_int), ("safeguard_warmup", C.c_int), ("pad", C.c_int)]
 
 
+class SfGroup(C.Structure):
+    _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong)] + [
+        (n, C.c_float) for n in ("lr", "a_y", "ckp1", "beta2", "one_minus_beta2", "inv_bc2", "eps", "weight_decay")] + [
+        ("first", C.c_int), ("pad", C.c_int)]
+
+
+class SfSwapGroup(C.Structure):
+    _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("w", C.c_float), ("pad", C.c_int)]
+
+
 class LoraShadowEntry(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("rows", C.c_int), ("cols", C.c_int),
                 ("dst_ld", C.c_int), ("scale", C.c_float), ("transpose", C.c_int), ("pad", C.c_int)]
@@ -169,6 +179,11 @@ SIGNATURES: dict[str, list] = {
     "otamd_prodigy_apply": [VP, VP, VP, I, VP, VP, LL, VP, C.POINTER(ProdigyHyper), VP, I, C.c_ulonglong, VP],
     "otamd_prodigy_state_size": [],
     "otamd_prodigy_hyper_size": [],
+    # schedule_free.hip
+    "otamd_sf_adamw_step": [VP, VP, VP, I, VP, VP, LL, LL, LL, C.POINTER(SfGroup), I, VP, I, C.c_ulonglong, VP],
+    "otamd_sf_swap": [VP, VP, I, VP, LL, LL, LL, C.POINTER(SfSwapGroup), I, VP],
+    "otamd_sf_group_size": [],
+    "otamd_sf_swap_group_size": [],
     # ema.hip
     "otamd_ema_range": [VP, VP, I, LL, LL, F, VP],
     "otamd_ema_sweep_elems": [I],
@@ -307,4 +322,6 @@ def check_layouts():
     assert L.otamd_came_fold_size() == C.sizeof(CameFold)
     assert L.otamd_prodigy_state_size() == C.sizeof(ProdigyState)
     assert L.otamd_prodigy_hyper_size() == C.sizeof(ProdigyHyper)
+    assert L.otamd_sf_group_size() == C.sizeof(SfGroup)
+    assert L.otamd_sf_swap_group_size() == C.sizeof(SfSwapGroup)
     assert L.otamd_dora_entry_size() == C.sizeof(DoraEntry)

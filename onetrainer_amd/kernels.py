@@ -1003,6 +1003,58 @@ def prodigy_apply(p, g, w, m, v, state, hyper, clip_coef=None, stochastic_roundi
           "otamd_prodigy_apply")
 
 
+def _sf_checks(p, w, z, others, f32, groups, begin, end):
+    """the argument checks sf_adamw_step and sf_swap share; returns (form, end).  others: further buffers in p's
+    layout whatever their dtype; f32: fp32 states indexed as the store; groups: SfGroup / SfSwapGroup sorted by begin."""
+    n = p.numel()
+    end = n if end is None else end
+    for t in (p,) + tuple(others) + ((w,) if w is not None else ()):
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t),
+             "schedule-free flat buffers")
+    for t in (z,) + tuple(f32):
+        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == n and _aligned(t),
+             "schedule-free fp32 states, indexed as the store")
+    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0,
+         "schedule-free range: multiples of 8 within the store")
+    _req(1 <= len(groups) <= 8, "schedule-free: one to eight parameter groups")
+    prev = 0
+    for g in groups:
+        _req(prev <= g.begin <= g.end <= n and g.begin % 8 == 0,
+             "schedule-free groups: sorted, disjoint ranges of the store that begin on a multiple of 8")
+        prev = g.end
+    return end
+
+
+def sf_adamw_step(p, g, w, z, v, groups, clip_coef=None, stochastic_rounding=False, seed=0, begin=0, end=None):
+    """one fused schedule-free AdamW step (csrc/schedule_free.hip) over elements [begin, end) of the store (default:
+    all).  p / g / w as prodigy_form (bf16 store; fp32 store; fp32 master p with bf16 gradients and the bf16 working
+    copy w); z, v: fp32 states indexed as the store; groups: _lib.SfGroup sorted by begin, scalars from the host."""
+    form = prodigy_form(p, g, w)
+    end = _sf_checks(p, w, z, (g,), (v,), groups, begin, end)
+    _req(clip_coef is None or (clip_coef.is_cuda and clip_coef.dtype == F32 and clip_coef.numel() >= 1),
+         "schedule-free clip coefficient: a device fp32 scalar")
+    arr = (_lib.SfGroup * len(groups))(*groups)
+    check(lib().otamd_sf_adamw_step(_p(p), _p(w), _p(g), form, _p(z), _p(v), p.numel(), begin, end, arr, len(groups),
+                                    _p(clip_coef), int(stochastic_rounding), seed & 0xFFFFFFFFFFFFFFFF,
+                                    stream_handle()),
+          "otamd_sf_adamw_step")
+
+
+def sf_swap(p, w, z, groups, begin=0, end=None):
+    """p <- p + w_group (z - p) over the groups' ranges inside [begin, end): the eval() / train() switch of the
+    schedule-free optimizer.  p / w as above (a bf16 store is rounded to nearest); groups: _lib.SfSwapGroup."""
+    if w is not None:
+        _req(p.dtype == F32 and w.dtype == BF16, "schedule-free master: fp32 p and its bf16 working copy")
+        form = 2
+    else:
+        _req(p.dtype in (BF16, F32), "schedule-free: a bf16 or fp32 store")
+        form = 0 if p.dtype == BF16 else 1
+    end = _sf_checks(p, w, z, (), (), groups, begin, end)
+    arr = (_lib.SfSwapGroup * len(groups))(*groups)
+    check(lib().otamd_sf_swap(_p(p), _p(w), form, _p(z), p.numel(), begin, end, arr, len(groups), stream_handle()),
+          "otamd_sf_swap")
+
+
 def ema_form(ema, p) -> int:
     """the C-ABI form code of csrc/ema.hip: 0 bf16 shadow of bf16 parameters, 1 fp32 / fp32, 2 fp32 shadow of bf16
     parameters."""

@@ -101,6 +101,29 @@ class GenericTrainer(TimedActionMixin):
         if StepGraphs.enabled_for(self):
             self.graphs = StepGraphs(self)
         self._attach_norm_overlap()
+        # GenericTrainer.py:603-606: a schedule-free optimizer starts (and a backup's state resumes) outside train
+        # mode; the loaded weights of a backup are the averaged x, which train() turns back into y
+        self._after_eval()
+
+    def _refresh_derived(self):
+        """what the setup derives from the parameters (LoRA bf16 shadows, the DoRA merge), after they were swapped"""
+        self.model_setup.after_optimizer_step(self.model, self.config, self.model.train_progress)
+
+    def _before_eval(self):
+        """the reference's __before_eval (GenericTrainer.py:560-566, and 414-417, 470-473, 772-775): a schedule-free
+        optimizer holds the gradient point y while training and the model to write is the average x.  Every rank
+        swaps (the ranks' stores stay equal); only rank 0 writes."""
+        opt = getattr(self.model, "optimizer", None)
+        if hasattr(opt, "eval"):
+            opt.eval()
+            self._refresh_derived()
+
+    def _after_eval(self):
+        """back to the gradient point (GenericTrainer.py:446-449, 481-483, 603-606)"""
+        opt = getattr(self.model, "optimizer", None)
+        if hasattr(opt, "train"):
+            opt.train()
+            self._refresh_derived()
 
     def _attach_norm_overlap(self):
         """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor, CAME, Prodigy): clip_grad_norm_'s norm pass runs during backward
@@ -153,6 +176,7 @@ class GenericTrainer(TimedActionMixin):
         if self.world > 1:
             torch.distributed.barrier()
         path = None
+        self._before_eval()
         if self.rank == 0:
             name = f"{datetime.now().strftime('%Y-%m-%d_%H-%M-%S')}-backup-{tp.filename_string()}"
             path = os.path.join(cfg.workspace_dir, "backup", name)
@@ -171,6 +195,7 @@ class GenericTrainer(TimedActionMixin):
             finally:
                 if cfg.rolling_backup:
                     self._prune_backups(cfg.rolling_backup_count)
+        self._after_eval()
         if self.world > 1:
             torch.distributed.barrier()
         return path
@@ -199,6 +224,8 @@ class GenericTrainer(TimedActionMixin):
             print_cb("Saving " + path)
         # GenericTrainer.py:467,494: the averaged weights are what a save holds; the trained ones wait on the host
         # and come back whether or not the write succeeded.  Only the writing rank swaps.
+        # A schedule-free optimizer switches to its averaged weights first (GenericTrainer.py:470-473) and back last.
+        self._before_eval()
         ema = getattr(self.model, "ema", None) if self.rank == 0 else None
         if ema is not None:
             ema.copy_ema_to(store_temp=True)
@@ -207,6 +234,7 @@ class GenericTrainer(TimedActionMixin):
         finally:
             if ema is not None:
                 ema.copy_temp_to()
+            self._after_eval()
 
     def _write_model(self, path: str, fmt: str) -> str | None:
         import os
@@ -493,6 +521,7 @@ class GenericTrainer(TimedActionMixin):
         cfg = self.config
         if cfg.backup_before_save:
             self.backup(self.model.train_progress)
+        self._before_eval()   # GenericTrainer.py:772-775: the final model is the averaged one; eval mode stays
         if getattr(self.model, "ema", None) is not None:   # GenericTrainer.py:779-780: the final, averaged model
             self.model.ema.copy_ema_to(store_temp=False)
         path = self.final_model_path()

@@ -37,6 +37,9 @@ class OptimizerConfig:
     growth_rate: float | None = None
     fsdp_in_use: bool | None = None
     slice_p: int | None = None
+    # SCHEDULE_FREE_ADAMW (None resolves as modules/util/create.py:759-766 does)
+    r: float | None = None
+    weight_lr_power: float | None = None
     stochastic_rounding: bool = True
     fused_back_pass: bool = False
     foreach: bool | None = False

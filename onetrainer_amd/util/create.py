@@ -1,5 +1,5 @@
 """Factories (mirrors the parts of modules/util/create.py the hot path uses:
-create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 863-881 (PRODIGY), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
+create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 752-767 (SCHEDULE_FREE_ADAMW), 863-881 (PRODIGY), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
 1114-1232, create_noise_scheduler 1235-1373)."""
 from __future__ import annotations
 
@@ -155,10 +155,21 @@ def check_prodigy(o, oc, groups):
                                   "not supported (d is one estimate for the whole store)")
 
 
+def schedule_free_options(oc) -> dict:
+    """OptimizerConfig -> schedulefree.AdamWScheduleFree arguments, None resolved exactly as create.py:759-766
+    resolves it (warmup_steps is not an optimizer option there: it is config.learning_rate_warmup_steps)."""
+    def pick(name, default):
+        v = getattr(oc, name, None)
+        return v if v is not None else default
+    return dict(beta1=pick("beta1", 0.9), beta2=pick("beta2", 0.999), weight_decay=pick("weight_decay", 1e-2),
+                eps=pick("eps", 1e-8), r=pick("r", 0), weight_lr_power=pick("weight_lr_power", 2.0),
+                foreach=pick("foreach", False))
+
+
 def create_optimizer(store, groups, config):
     """the fused optimizer over `store` for config.optimizer (create.py:509-534 ADAMW + patch_adamw, 914-936
-    ADAFACTOR + patch_adafactor, 938-951 CAME, 863-881 PRODIGY).  Anything else is refused: there is no eager
-    fall-back."""
+    ADAFACTOR + patch_adafactor, 938-951 CAME, 863-881 PRODIGY, 752-767 SCHEDULE_FREE_ADAMW).  Anything else is
+    refused: there is no eager fall-back."""
     config = plain(config)
     oc = config.optimizer
     name = str(oc.optimizer)
@@ -196,8 +207,22 @@ def create_optimizer(store, groups, config):
                             use_bias_correction=o["use_bias_correction"], safeguard_warmup=o["safeguard_warmup"],
                             d0=o["d0"], d_coef=o["d_coef"], growth_rate=o["growth_rate"],
                             stochastic_rounding=bool(oc.stochastic_rounding))
+    if name == "SCHEDULE_FREE_ADAMW":
+        o = schedule_free_options(oc)
+        if getattr(oc, "fused_back_pass", False):
+            raise NotImplementedError("SCHEDULE_FREE_ADAMW fused_back_pass: the reference offers the fused back pass "
+                                      "for other optimizers only")
+        from .optimizer.schedule_free_fused import FusedScheduleFreeAdamW
+        # create.py:763: the raw warm-up steps, not divided by the gradient accumulation; the LR scheduler's own
+        # warm-up drives group['lr'] on top of it, as in the reference
+        return FusedScheduleFreeAdamW(store, groups, lr=config.learning_rate, betas=(o["beta1"], o["beta2"]),
+                                      weight_decay=o["weight_decay"], eps=o["eps"],
+                                      warmup_steps=config.learning_rate_warmup_steps, r=o["r"],
+                                      weight_lr_power=o["weight_lr_power"], foreach=o["foreach"],
+                                      stochastic_rounding=bool(oc.stochastic_rounding))
     raise NotImplementedError(f"optimizer {name}: only ADAMW, ADAFACTOR and CAME (with a learning rate of "
-                              "your choice) and PRODIGY (which estimates it) are on the hot path")
+                              "your choice), PRODIGY (which estimates it) and SCHEDULE_FREE_ADAMW (which needs no "
+                              "schedule) are on the hot path")
 
 
 def create_ema(store, state_dict, config):
