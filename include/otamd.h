@@ -148,6 +148,19 @@ typedef struct SfGroup {
 } SfGroup;
 typedef struct SfSwapGroup { long long begin, end; float w; int pad; } SfSwapGroup;
 
+/* 8-bit AdamW (csrc/adamw8bit.hip).  A8Seg: one tensor of the store, a host-built table sorted by begin: element range
+   [begin, end) (begin a multiple of 8), blk0 its first 256-element work block (numbered consecutively through the
+   table), state_off its first absmax entry (is8bit) or its first element in the fp32 side buffers (a multiple of 8),
+   group the index of its A8Group.  A8Group: the scalars of one parameter group, by value from the host: beta1,
+   1 - beta1, beta2, 1 - beta2, eps_c = sqrt(bc2) eps, step_size = -lr sqrt(bc2) / bc1, wd_factor = 1 - lr wd. */
+typedef struct A8Seg {
+  long long begin, end, blk0, state_off;
+  int is8bit, group;
+} A8Seg;
+typedef struct A8Group {
+  float beta1, one_minus_beta1, beta2, one_minus_beta2, eps_c, step_size, wd_factor, pad;
+} A8Group;
+
 /* replaces: diffusers Linear/Conv2d fwd+bwd inside model.unet(...) (modules/modelSetup/BaseStableDiffusionXLSetup.py:268-273); conv/linear dgrad/wgrad of loss.backward() (modules/trainer/GenericTrainer.py:693-696) */
 int otamd_gemm(const GemmArgs* in, int splits, void* workspace, long long ws_bytes, hipStream_t stream);
 
@@ -674,6 +687,34 @@ int otamd_sf_swap(void* p, void* w16, int form, const float* z, long long n, lon
 int otamd_sf_group_size(void);
 /* replaces: ABI check */
 int otamd_sf_swap_group_size(void);
+
+/* replaces: bnb.optim.AdamW8bit.step as modules/util/create.py:553-566 builds it (block-wise, two states, blocks of
+   256, dynamic-tree codebooks; bitsandbytes is not in the reference tree: the contract is the step restated in
+   tests/_oracle_adamw8bit.py).  One launch over every tensor of the table, one wave per block: m = map1[code1] absmax1,
+   v = map2[code2] absmax2 (tensors with is8bit 0 read fp32 m, v from m32 / v32), m = beta1 m + (1 - beta1) g,
+   v = beta2 v + ((1 - beta2) g) g, p = (p + step_size (m / (sqrt(v) + eps_c))) wd_factor, new absmax = max |m|, max v
+   over the block, new codes = the number of codebook midpoints strictly below m / absmax (0 / 0 taken as 0); every
+   fp32 operation one rounding, no fused multiply-add.  g after the pending clip (clip_coef, nullable; bf16-rounded in
+   form 0).  code1 / code2: uint8 indexed as the store (n elements; the padding is never written); absmax1 / absmax2:
+   n_absmax fp32; m32 / v32: n_f32 fp32; qmap: 512 fp32 on the device, the signed then the unsigned codebook, each
+   ascending.  table_dev / table_host: the same A8Seg[n_segs] on the device and on the host; the host copy is checked
+   on every call (otamd_adamw8bit_check) before anything is launched.  Forms as otamd_sf_adamw_step.  Workgroup cap
+   OTAMD_ADAMW_BLOCKS.  No atomics. */
+int otamd_adamw8bit_step(void* p, void* w16, const void* g, int form, void* code1, void* code2, float* absmax1,
+    float* absmax2, long long n_absmax, float* m32, float* v32, long long n_f32, const float* qmap, long long n,
+    const void* table_dev, const void* table_host, int n_segs, const A8Group* groups, int n_groups,
+    const float* clip_coef, int stochastic_rounding, unsigned long long seed, hipStream_t stream);
+
+/* replaces: nothing (the table check of otamd_adamw8bit_step, host code only: tensors sorted, disjoint and inside
+   the store of n elements, work blocks numbered consecutively from 0, state ranges of one kind ascending, disjoint and
+   inside their buffers, group < n_groups; OTAMD_EINVAL otherwise) */
+int otamd_adamw8bit_check(const A8Seg* table, int n_segs, long long n, long long n_absmax, long long n_f32,
+    int n_groups);
+
+/* replaces: ABI check */
+int otamd_adamw8bit_seg_size(void);
+/* replaces: ABI check */
+int otamd_adamw8bit_group_size(void);
 
 /* replaces: EMAModuleWrapper.step (modules/module/EMAModule.py:37-54), ema.add_(one_minus_decay * (parameter - ema))
    per tensor, for elements [begin, end) of the flat buffers (multiples of 8, 16-byte aligned pointers; padding is 0

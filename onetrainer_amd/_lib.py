@@ -100,6 +100,16 @@ class SfSwapGroup(C.Structure):
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("w", C.c_float), ("pad", C.c_int)]
 
 
+class A8Seg(C.Structure):
+    _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("blk0", C.c_longlong), ("state_off", C.c_longlong),
+                ("is8bit", C.c_int), ("group", C.c_int)]
+
+
+class A8Group(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "eps_c", "step_size",
+                                         "wd_factor", "pad")]
+
+
 class LoraShadowEntry(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("rows", C.c_int), ("cols", C.c_int),
                 ("dst_ld", C.c_int), ("scale", C.c_float), ("transpose", C.c_int), ("pad", C.c_int)]
@@ -184,6 +194,12 @@ SIGNATURES: dict[str, list] = {
     "otamd_sf_swap": [VP, VP, I, VP, LL, LL, LL, C.POINTER(SfSwapGroup), I, VP],
     "otamd_sf_group_size": [],
     "otamd_sf_swap_group_size": [],
+    # adamw8bit.hip
+    "otamd_adamw8bit_step": [VP, VP, VP, I, VP, VP, VP, VP, LL, VP, VP, LL, VP, LL, VP, VP, I, C.POINTER(A8Group), I,
+                             VP, I, C.c_ulonglong, VP],
+    "otamd_adamw8bit_check": [VP, I, LL, LL, LL, I],
+    "otamd_adamw8bit_seg_size": [],
+    "otamd_adamw8bit_group_size": [],
     # ema.hip
     "otamd_ema_range": [VP, VP, I, LL, LL, F, VP],
     "otamd_ema_sweep_elems": [I],
@@ -324,4 +340,6 @@ def check_layouts():
     assert L.otamd_prodigy_hyper_size() == C.sizeof(ProdigyHyper)
     assert L.otamd_sf_group_size() == C.sizeof(SfGroup)
     assert L.otamd_sf_swap_group_size() == C.sizeof(SfSwapGroup)
+    assert L.otamd_adamw8bit_seg_size() == C.sizeof(A8Seg)
+    assert L.otamd_adamw8bit_group_size() == C.sizeof(A8Group)
     assert L.otamd_dora_entry_size() == C.sizeof(DoraEntry)

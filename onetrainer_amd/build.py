@@ -32,6 +32,7 @@ EXTRA = {
     "came.hip": ["-ffp-contract=off"],
     "prodigy.hip": ["-ffp-contract=off"],
     "schedule_free.hip": ["-ffp-contract=off"],
+    "adamw8bit.hip": ["-ffp-contract=off"],
     "diffusion.hip": ["-ffp-contract=off"],
     "ema.hip": ["-ffp-contract=off"],
     # no NaN canonicalisation (v_max_f32 x, x) in front of every fmaxf on an MFMA result: one extra

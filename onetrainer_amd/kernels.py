@@ -1055,6 +1055,43 @@ def sf_swap(p, w, z, groups, begin=0, end=None):
           "otamd_sf_swap")
 
 
+def adamw8bit_check(table_host, n_segs, n, n_absmax, n_f32, n_groups) -> int:
+    """the table check of adamw8bit_step alone (host code, launches nothing): the library's status code"""
+    return int(lib().otamd_adamw8bit_check(C.cast(table_host, C.c_void_p), int(n_segs), int(n), int(n_absmax),
+                                           int(n_f32), int(n_groups)))
+
+
+def adamw8bit_step(p, g, w, code1, code2, absmax1, absmax2, m32, v32, qmap, table, table_host, n_segs, groups,
+                   clip_coef=None, stochastic_rounding=False, seed=0):
+    """one fused 8-bit AdamW step (csrc/adamw8bit.hip) over every tensor of the segment table.  p / g / w as
+    prodigy_form; code1 / code2: uint8 indexed as the store; absmax1 / absmax2: fp32 per 256-element block; m32 / v32:
+    the fp32 moments of the tensors below min_8bit_size; qmap: 512 fp32, the signed then the unsigned codebook.
+    table: device bytes of _lib.A8Seg[n_segs]; table_host: the same array as a ctypes object (checked by the library on
+    every call); groups: _lib.A8Group indexed by the segments' `group`."""
+    form = prodigy_form(p, g, w)
+    n = p.numel()
+    for t in (p, g) + ((w,) if w is not None else ()):
+        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "adamw8bit flat buffers")
+    for t in (code1, code2):
+        _req(t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and _aligned(t),
+             "adamw8bit codes: uint8, indexed as the store")
+    _req(absmax1.numel() == absmax2.numel() and m32.numel() == v32.numel(), "adamw8bit states: pairs of one size")
+    for t in (absmax1, absmax2, m32, v32, qmap):
+        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), "adamw8bit fp32 states")
+    _req(qmap.numel() == 512, "adamw8bit codebooks: 2 x 256 fp32")
+    _req(table.is_cuda and table.dtype == torch.uint8 and table.numel() == n_segs * C.sizeof(_lib.A8Seg) and n_segs >= 1,
+         "adamw8bit table")
+    _req(1 <= len(groups) <= 8, "adamw8bit: one to eight parameter groups")
+    _req(clip_coef is None or (clip_coef.is_cuda and clip_coef.dtype == F32 and clip_coef.numel() >= 1),
+         "adamw8bit clip coefficient: a device fp32 scalar")
+    arr = (_lib.A8Group * len(groups))(*groups)
+    check(lib().otamd_adamw8bit_step(_p(p), _p(w), _p(g), form, _p(code1), _p(code2), _p(absmax1), _p(absmax2),
+                                     absmax1.numel(), _p(m32), _p(v32), m32.numel(), _p(qmap), n, _p(table),
+                                     C.cast(table_host, C.c_void_p), n_segs, arr, len(groups), _p(clip_coef),
+                                     int(stochastic_rounding), seed & 0xFFFFFFFFFFFFFFFF, stream_handle()),
+          "otamd_adamw8bit_step")
+
+
 def ema_form(ema, p) -> int:
     """the C-ABI form code of csrc/ema.hip: 0 bf16 shadow of bf16 parameters, 1 fp32 / fp32, 2 fp32 shadow of bf16
     parameters."""

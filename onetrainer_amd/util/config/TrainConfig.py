@@ -40,6 +40,11 @@ class OptimizerConfig:
     # SCHEDULE_FREE_ADAMW (None resolves as modules/util/create.py:759-766 does)
     r: float | None = None
     weight_lr_power: float | None = None
+    # ADAMW_8BIT (None resolves as modules/util/create.py:558-565 does)
+    min_8bit_size: int | None = None
+    percentile_clipping: int | None = None
+    block_wise: bool | None = None
+    is_paged: bool | None = None
     stochastic_rounding: bool = True
     fused_back_pass: bool = False
     foreach: bool | None = False

@@ -1,5 +1,5 @@
 """Factories (mirrors the parts of modules/util/create.py the hot path uses:
-create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 752-767 (SCHEDULE_FREE_ADAMW), 863-881 (PRODIGY), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
+create_model_setup 285-353, create_optimizer 509-534 (ADAMW), 553-566 (ADAMW_8BIT), 752-767 (SCHEDULE_FREE_ADAMW), 863-881 (PRODIGY), 914-936 (ADAFACTOR) and 938-951 (CAME), create_lr_scheduler
 1114-1232, create_noise_scheduler 1235-1373)."""
 from __future__ import annotations
 
@@ -166,10 +166,39 @@ def schedule_free_options(oc) -> dict:
                 foreach=pick("foreach", False))
 
 
+def adamw8bit_options(oc) -> dict:
+    """OptimizerConfig -> bnb.optim.AdamW8bit arguments, None resolved exactly as create.py:558-565 resolves it"""
+    def pick(name, default):
+        v = getattr(oc, name, None)
+        return v if v is not None else default
+    return dict(beta1=pick("beta1", 0.9), beta2=pick("beta2", 0.999), weight_decay=pick("weight_decay", 1e-2),
+                eps=pick("eps", 1e-8), min_8bit_size=pick("min_8bit_size", 4096),
+                percentile_clipping=pick("percentile_clipping", 100), block_wise=pick("block_wise", True),
+                is_paged=pick("is_paged", False))
+
+
+def check_adamw8bit(o, oc, lr, groups):
+    """what the fused 8-bit AdamW does not do, refused by the option's name before anything is allocated"""
+    if not o["block_wise"]:
+        raise NotImplementedError("ADAMW_8BIT block_wise=False: only the block-wise quantisation (blocks of 256) is "
+                                  "on the hot path")
+    if o["percentile_clipping"] != 100:
+        raise NotImplementedError(f"ADAMW_8BIT percentile_clipping={o['percentile_clipping']}: only 100 (no "
+                                  "percentile clipping of the gradient norm) is on the hot path")
+    if o["is_paged"]:
+        raise NotImplementedError("ADAMW_8BIT is_paged: paged optimizer state is not supported (the state stays in "
+                                  "device memory)")
+    if getattr(oc, "fused_back_pass", False):
+        raise NotImplementedError("ADAMW_8BIT fused_back_pass: the 8-bit step is one launch over the whole store")
+    from .optimizer.adamw8bit_fused import check_hyper
+    for lr_ in [lr] + [g["lr"] for g in groups if "lr" in g]:
+        check_hyper(dict(betas=(o["beta1"], o["beta2"]), eps=o["eps"], lr=lr_, weight_decay=o["weight_decay"]))
+
+
 def create_optimizer(store, groups, config):
     """the fused optimizer over `store` for config.optimizer (create.py:509-534 ADAMW + patch_adamw, 914-936
-    ADAFACTOR + patch_adafactor, 938-951 CAME, 863-881 PRODIGY, 752-767 SCHEDULE_FREE_ADAMW).  Anything else is
-    refused: there is no eager fall-back."""
+    ADAFACTOR + patch_adafactor, 938-951 CAME, 863-881 PRODIGY, 752-767 SCHEDULE_FREE_ADAMW, 553-566 ADAMW_8BIT).
+    Anything else is refused: there is no eager fall-back."""
     config = plain(config)
     oc = config.optimizer
     name = str(oc.optimizer)
@@ -220,9 +249,16 @@ def create_optimizer(store, groups, config):
                                       warmup_steps=config.learning_rate_warmup_steps, r=o["r"],
                                       weight_lr_power=o["weight_lr_power"], foreach=o["foreach"],
                                       stochastic_rounding=bool(oc.stochastic_rounding))
+    if name == "ADAMW_8BIT":
+        o = adamw8bit_options(oc)
+        check_adamw8bit(o, oc, config.learning_rate, groups)
+        from .optimizer.adamw8bit_fused import FusedAdamW8bit
+        return FusedAdamW8bit(store, groups, lr=config.learning_rate, betas=(o["beta1"], o["beta2"]),
+                              weight_decay=o["weight_decay"], eps=o["eps"], min_8bit_size=o["min_8bit_size"],
+                              stochastic_rounding=bool(oc.stochastic_rounding))
     raise NotImplementedError(f"optimizer {name}: only ADAMW, ADAFACTOR and CAME (with a learning rate of "
-                              "your choice), PRODIGY (which estimates it) and SCHEDULE_FREE_ADAMW (which needs no "
-                              "schedule) are on the hot path")
+                              "your choice), PRODIGY (which estimates it), SCHEDULE_FREE_ADAMW (which needs no "
+                              "schedule) and ADAMW_8BIT (block-wise 8-bit moments) are on the hot path")
 
 
 def create_ema(store, state_dict, config):

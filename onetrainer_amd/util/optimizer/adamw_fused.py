@@ -35,8 +35,8 @@ class FlatStoreOptimizer(torch.optim.Optimizer):
     """What every fused optimizer over a FlatParamStore shares: the parameter groups as contiguous element ranges,
     the per-tensor chunk table of the global grad norm, clip_grad_norm_ (whose coefficient stays on the device and is
     applied inside the next step()) and the hook OverlappedGradNorm attaches to.  FusedAdamW, FusedAdafactor
-    (adafactor_fused.py), FusedCAME (came_fused.py), FusedProdigy (prodigy_fused.py) and FusedScheduleFreeAdamW
-    (schedule_free_fused.py) derive from it."""
+    (adafactor_fused.py), FusedCAME (came_fused.py), FusedProdigy (prodigy_fused.py), FusedScheduleFreeAdamW
+    (schedule_free_fused.py) and FusedAdamW8bit (adamw8bit_fused.py) derive from it."""
 
     def _init_store(self, store):
         self.store = store
