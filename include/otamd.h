@@ -547,6 +547,26 @@ int otamd_diffusion_loss(const void* pred, int cpad, const void* target, int tgt
 int otamd_diffusion_loss_grad(const void* pred, int cpad, const void* target, int tgt_f32, const float* mask, int B,
     long long HW, int C, float unmasked_weight, const float* coef, const float* grad_out, void* dpred, hipStream_t s);
 
+/* replaces: the per-step math of the sampler loop (modules/modelSampler/StableDiffusionXLSampler.py:156-172) with the
+   DDIMScheduler of modules/util/create.py:1255-1266 at eta = 0, clip_sample False: p = neg + cfg (pos - neg); when
+   cfg_rescale > 0, p *= 1 + cfg_rescale (std(pos) / std(p) - 1) with torch's unbiased std over the sample's 4 HW real
+   elements (factor 1 for a sample whose p is constant, std(p) == 0); epsilon: x0 = (x - s1_t p) / sa_t, e = p; v_prediction: x0 = sa_t x - s1_t p, e = sa_t p + s1_t x;
+   x_prev = sa_p x0 + s1_p e, with sa = sqrt_acp[.] and s1 = sqrt_1m[.] at t and t_prev (the device tables of
+   NoiseScheduler.coeffs, n_table entries each).
+   pred: bf16 NHWC [2B, HW, 8] = [negative | positive], 4 real channels (the pad channels are not read into anything);
+   x: fp32 [B, HW, 4]; x_out: fp32 [B, HW, 4], may be x; next_in: bf16 [2B, HW, 8], both halves x_prev, pad channels 0.
+   ws: otamd_cfg_ddim_step_ws_bytes(B, HW) bytes, 8-byte aligned, read only when cfg_rescale > 0.  All tensors 16-byte
+   aligned.  Fixed-order reductions, no atomics: the same inputs give the same bits. */
+int otamd_cfg_ddim_step(const void* pred, const float* x, float* x_out, void* next_in, int B, long long HW,
+    float cfg_scale, float cfg_rescale, int v_pred, const float* sqrt_acp, const float* sqrt_1m, int n_table, int t,
+    int t_prev, void* ws, long long ws_bytes, hipStream_t s);
+long long otamd_cfg_ddim_step_ws_bytes(int B, long long HW);
+
+/* replaces: VaeImageProcessor.postprocess (denormalize + numpy_to_pil's (x * 255).round()) on the decoder output
+   (StableDiffusionXLSampler.py:188-189); the inverse of otamd_image_to_nhwc: x bf16 [npix, cpad] (R, G, B first) ->
+   out uint8 [npix, 3] = round(clamp(x / 2 + 0.5, 0, 1) * 255), ties to even.  out 4-byte aligned. */
+int otamd_nhwc_to_rgb8(const void* x, int cpad, long long npix, void* out, hipStream_t s);
+
 /* replaces: AdamW step_adamw_parameter + addcdiv_stochastic_ (modules/util/optimizer/adamw_extensions.py:17-150; modules/util/bf16_stochastic_rounding.py:5-61), patched at modules/util/create.py:509-534 */
 int otamd_adamw_bf16(void* p, const void* g, void* m, void* v, long long n, const AdamwGroup* groups, int
     n_groups, const float* clip_coef, int stochastic_rounding, unsigned long long seed, hipStream_t stream);

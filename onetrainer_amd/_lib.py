@@ -288,6 +288,10 @@ SIGNATURES: dict[str, list] = {
     "otamd_diffusion_loss": [VP, I, VP, I, VP, I, LL, I, F, F, F, F, I, F, VP, VP, VP, VP, I, F, I, I, F, VP, LL, VP,
                              VP, VP, VP],
     "otamd_diffusion_loss_grad": [VP, I, VP, I, VP, I, LL, I, F, VP, VP, VP, VP],
+    # sampler.hip
+    "otamd_cfg_ddim_step": [VP, VP, VP, VP, I, LL, F, F, I, VP, VP, I, I, I, VP, LL, VP],
+    "otamd_cfg_ddim_step_ws_bytes": [I, LL],
+    "otamd_nhwc_to_rgb8": [VP, I, LL, VP, VP],
 }
 
 _lib = None

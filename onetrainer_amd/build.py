@@ -35,6 +35,7 @@ EXTRA = {
     "adamw8bit.hip": ["-ffp-contract=off"],
     "diffusion.hip": ["-ffp-contract=off"],
     "ema.hip": ["-ffp-contract=off"],
+    "sampler.hip": ["-ffp-contract=off"],
     # no NaN canonicalisation (v_max_f32 x, x) in front of every fmaxf on an MFMA result: one extra
     # VALU per softmax score; the kernels never produce or test NaNs (masked keys are -inf)
     # no SLP packing of the softmax's f32 math into v_pk_*_f32, which costs more than two single-issue ops

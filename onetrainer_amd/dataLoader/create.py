@@ -186,8 +186,9 @@ def create_data_loader(config, model, device, rank: int = 0, world: int = 1):
         build_cache(cfg, model, device, rank)
         if world > 1:
             torch.distributed.barrier()
+        keep = ("text_encoder_1", "text_encoder_2") if getattr(model, "keep_text_encoders", False) else ()
         for attr in ("vae_encoder", "text_encoder_1", "text_encoder_2"):   # caching done: free the encoders
-            if hasattr(model, attr):
+            if hasattr(model, attr) and attr not in keep:   # (the sampler keeps the text encoders for its prompts)
                 setattr(model, attr, None)
         if torch.cuda.is_available():
             torch.cuda.empty_cache()

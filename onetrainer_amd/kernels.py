@@ -1784,6 +1784,62 @@ def flow_prologue(latent, noise_, timestep, scaling_factor, shift_factor, num_t=
     return model_in, target
 
 
+# ------------------------------------------------------------------------------------------
+# sampling kernels (csrc/sampler.hip)
+def cfg_ddim_step(pred, x, coeffs, t, t_prev, cfg_scale, cfg_rescale=0.0, v_pred=False, out=None, next_in=None):
+    """classifier-free guidance, CFG rescale and one DDIM step (eta 0) of the sampler loop.
+    pred: UNet output bf16 NHWC [2B, h, w, 8] = [negative | positive] (4 real channels); x: fp32 [B, h, w, 4];
+    coeffs: NoiseScheduler.coeffs (device tables); t / t_prev: table indices of this step's alpha_t / alpha_prev.
+    -> (x_prev fp32 [B, h, w, 4] (written to `out`, which may be x), next UNet input bf16 [2B, h, w, 8])."""
+    _req(pred.dim() == 4 and pred.dtype == BF16 and pred.is_cuda and pred.is_contiguous() and pred.shape[-1] == 8
+         and pred.shape[0] % 2 == 0 and pred.shape[0] > 0, "cfg_ddim_step pred: contiguous bf16 cuda [2B, h, w, 8]")
+    B2, h, w, _ = pred.shape
+    B = B2 // 2
+    _req(h * w > 0 and B <= 32767, "cfg_ddim_step pred: empty image or more than 32767 samples")
+    _req(x.dtype == F32 and x.is_contiguous() and tuple(x.shape) == (B, h, w, 4) and x.device == pred.device,
+         "cfg_ddim_step x: contiguous fp32 [B, h, w, 4] on pred's device")
+    out = torch.empty_like(x) if out is None else out
+    _req(out.dtype == F32 and out.is_contiguous() and out.shape == x.shape and out.device == x.device,
+         "cfg_ddim_step out: like x")
+    next_in = torch.empty_like(pred) if next_in is None else next_in
+    _req(next_in.dtype == BF16 and next_in.is_contiguous() and next_in.shape == pred.shape
+         and next_in.device == pred.device and next_in.data_ptr() != pred.data_ptr(),
+         "cfg_ddim_step next_in: like pred, and not pred itself")
+    _, sq, s1m = coeffs
+    n_table = sq.numel()
+    _req(sq.dtype == F32 and s1m.dtype == F32 and sq.is_contiguous() and s1m.is_contiguous()
+         and s1m.numel() == n_table and sq.device == pred.device and s1m.device == pred.device,
+         "cfg_ddim_step coeffs: fp32 tables of one length on pred's device")
+    t, t_prev = int(t), int(t_prev)
+    _req(0 <= t < n_table and 0 <= t_prev < n_table, f"cfg_ddim_step: timesteps {t}, {t_prev} outside the table")
+    cfg_rescale = float(cfg_rescale)
+    _req(cfg_rescale >= 0.0 and math.isfinite(cfg_rescale) and math.isfinite(float(cfg_scale)),
+         "cfg_ddim_step: cfg_scale finite, cfg_rescale finite and >= 0")
+    _req(all(a.data_ptr() % 16 == 0 for a in (pred, x, out, next_in)), "cfg_ddim_step: 16-byte aligned tensors")
+    ws, nbytes = None, 0
+    if cfg_rescale > 0:
+        nbytes = lib().otamd_cfg_ddim_step_ws_bytes(B, h * w)
+        ws = workspace(nbytes, pred.device)
+    check(lib().otamd_cfg_ddim_step(_p(pred), _p(x), _p(out), _p(next_in), B, h * w, float(cfg_scale), cfg_rescale,
+                                    int(bool(v_pred)), _p(sq), _p(s1m), n_table, t, t_prev, _p(ws), nbytes,
+                                    stream_handle()), "otamd_cfg_ddim_step")
+    return out, next_in
+
+
+def nhwc_to_rgb8(x, out=None):
+    """decoder output bf16 NHWC [B, H, W, cpad >= 3] in [-1, 1] -> uint8 [B, H, W, 3] =
+    round(clamp(x / 2 + 0.5, 0, 1) * 255); the inverse of image_to_nhwc."""
+    _req(x.dim() == 4 and x.dtype == BF16 and x.is_cuda and x.is_contiguous() and x.shape[-1] >= 3 and x.numel() > 0,
+         "nhwc_to_rgb8: contiguous bf16 cuda [B, H, W, >= 3]")
+    B, H, W, cpad = x.shape
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device) if out is None else out
+    _req(out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, H, W, 3)
+         and out.device == x.device and out.data_ptr() % 4 == 0, "nhwc_to_rgb8 out: contiguous uint8 [B, H, W, 3]")
+    _req(cpad != 8 or x.data_ptr() % 16 == 0, "nhwc_to_rgb8: 16-byte aligned input")
+    check(lib().otamd_nhwc_to_rgb8(_p(x), cpad, B * H * W, _p(out), stream_handle()), "otamd_nhwc_to_rgb8")
+    return out
+
+
 LOSS_FN = {"CONSTANT": 0, "MIN_SNR_GAMMA": 1, "DEBIASED_ESTIMATION": 2, "P2": 3, "SIGMA": 4}
 
 

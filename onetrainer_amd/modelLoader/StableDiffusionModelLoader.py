@@ -74,6 +74,38 @@ def load_vae_encoder(encoder, name: str) -> None:
     apply_vae_state_dict(encoder, LC.vae_from_ldm(read_single_file(name), encoder.specs))
 
 
+def apply_vae_decoder_state_dict(decoder, sd: dict) -> None:
+    sd = LC.fix_legacy_vae_keys(sd)
+    missing = [n for n, *_ in decoder.specs if n not in sd]
+    if missing:
+        raise KeyError(f"{len(missing)} VAE decoder parameters missing, e.g. {missing[:3]}")
+    decoder.load_state_dict({n: sd[n].reshape(shape) for n, shape, *_ in decoder.specs})
+
+
+def load_vae_decoder(decoder, name: str) -> None:
+    """the VAE decoder of the training samples (module/vae.AutoencoderKLDecoder) from the same places"""
+    if os.path.isdir(name):
+        for sub in ("vae", None):
+            try:
+                apply_vae_decoder_state_dict(decoder, read_diffusers_sub_module(name, sub))
+                return
+            except (FileNotFoundError, KeyError):
+                continue
+        raise Exception("could not load vae: " + name)
+    apply_vae_decoder_state_dict(decoder, LC.vae_from_ldm(read_single_file(name), decoder.specs))
+
+
+def frozen_source(model, base: str, vae: str | None) -> tuple:
+    """(base, vae) the frozen modules of the training samples -- the VAE decoder and the sampler's text encoders --
+    load from.  A run that continues from a backup loads its UNet from the backup directory, which holds neither
+    (the saver writes what was trained): the trainer then names the run's original base / VAE model in
+    `model.sampling_source`, and these modules come from there."""
+    src = getattr(model, "sampling_source", None)
+    if src is None or not (src.base_model or src.vae_model):
+        return base, vae
+    return src.base_model or base, src.vae_model or None
+
+
 def load_text_encoder(encoder, root: str, subfolder: str) -> None:
     """a transformers text encoder (`text_encoder/`, `text_encoder_2/`: model.safetensors, sharded
     index or pytorch_model.bin) into a module.text_encoder encoder; CLIP keys without the
@@ -101,10 +133,15 @@ class StableDiffusionXLModelLoader:
 
     def _load_diffusers(self, model, base: str, vae: str | None):
         apply_unet_state_dict(model.unet, read_diffusers_sub_module(base, "unet"))
-        load_text_encoders(model, base)
+        fbase, fvae = frozen_source(model, base, vae)
+        if os.path.isdir(fbase):
+            load_text_encoders(model, fbase)
         enc = getattr(model, "vae_encoder", None)
         if enc is not None:
             load_vae_encoder(enc, vae or base)
+        dec = getattr(model, "vae_decoder", None)   # attached only when samples are configured
+        if dec is not None:
+            load_vae_decoder(dec, fvae or fbase)
 
     def _load_internal(self, model, base: str, vae: str | None):
         if not os.path.isfile(os.path.join(base, "meta.json")):
@@ -123,6 +160,13 @@ class StableDiffusionXLModelLoader:
                 load_vae_encoder(enc, vae)
             else:
                 apply_vae_state_dict(enc, LC.vae_from_ldm(sd, enc.specs))
+        dec = getattr(model, "vae_decoder", None)
+        if dec is not None:
+            fbase, fvae = frozen_source(model, base, vae)
+            if fvae or fbase != base:
+                load_vae_decoder(dec, fvae or fbase)
+            else:   # the checkpoint just read
+                apply_vae_decoder_state_dict(dec, LC.vae_from_ldm(sd, dec.specs))
 
     def load(self, model, model_names) -> None:
         base, vae = model_names.base_model, model_names.vae_model or None

@@ -74,15 +74,31 @@ _VAE_RES = {"conv_shortcut": "nin_shortcut"}
 _VAE_ATTN = {"group_norm": "norm", "to_q": "q", "to_k": "k", "to_v": "v", "to_out.0": "proj_out"}
 
 
-def vae_ldm_name(name: str) -> str:
-    """encoder + quant_conv names (the decoder is not on the training path)."""
-    if name.startswith("quant_conv."):
+def vae_ldm_name(name: str, n_blocks: int = 4) -> str:
+    """encoder + quant_conv names, and the decoder + post_quant_conv names the sampler's decoder loads (LDM counts
+    the decoder's `up` levels from the output side: up_blocks.i is up.{n_blocks - 1 - i})."""
+    if name.startswith(("quant_conv.", "post_quant_conv.")):
         return name
     mod, _, leaf = name.rpartition(".")
     fixed = {"encoder.conv_in": "encoder.conv_in", "encoder.conv_norm_out": "encoder.norm_out",
-             "encoder.conv_out": "encoder.conv_out"}
+             "encoder.conv_out": "encoder.conv_out", "decoder.conv_in": "decoder.conv_in",
+             "decoder.conv_norm_out": "decoder.norm_out", "decoder.conv_out": "decoder.conv_out"}
     if mod in fixed:
         return f"{fixed[mod]}.{leaf}"
+    m = re.match(r"decoder\.up_blocks\.(\d+)\.(resnets|upsamplers)\.(\d+)\.(.*)$", name)
+    if m:
+        i, kind, j, rest = n_blocks - 1 - int(m[1]), m[2], int(m[3]), m[4]
+        if kind == "upsamplers":
+            return f"decoder.up.{i}.upsample.{rest}"
+        head, _, lf = rest.partition(".")
+        return f"decoder.up.{i}.block.{j}.{_VAE_RES.get(head, head)}.{lf}"
+    m = re.match(r"decoder\.mid_block\.(resnets|attentions)\.(\d+)\.(.*)$", name)
+    if m:
+        kind, j, rest = m[1], int(m[2]), m[3]
+        if kind == "resnets":
+            return f"decoder.mid.block_{j + 1}.{rest}"
+        sub, _, lf = rest.rpartition(".")
+        return f"decoder.mid.attn_1.{_VAE_ATTN[sub]}.{lf}"
     m = re.match(r"encoder\.down_blocks\.(\d+)\.(resnets|downsamplers)\.(\d+)\.(.*)$", name)
     if m:
         i, kind, j, rest = int(m[1]), m[2], int(m[3]), m[4]
@@ -130,8 +146,10 @@ def unet_to_ldm(sd: dict, cfg) -> dict:
 def vae_from_ldm(sd: dict, specs) -> dict:
     """diffusers-named VAE encoder state dict; LDM attention q/k/v/proj_out are 1x1 convs."""
     out = {}
+    n_blocks = 1 + max([int(m[1]) for m in (re.match(r"decoder\.up_blocks\.(\d+)\.", n) for n, *_ in specs) if m],
+                       default=3)
     for name, shape, *_ in specs:
-        key = VAE_PREFIX + vae_ldm_name(name)
+        key = VAE_PREFIX + vae_ldm_name(name, n_blocks)
         if key in sd:
             out[name] = sd[key].reshape(shape)
     return out

@@ -45,7 +45,8 @@ def _span(t: torch.Tensor):
 _OUT_NAMES = {"out", "dx", "dq", "dk", "dv", "dgamma", "dbeta", "dmod", "dh", "grad_out", "bias_grad", "dw",
               "chunk_sq", "tensor_sq"}
 _OUT_EXTRA = {"gated_add_bwd": {"dy"}, "adamw_bf16": {"p", "m", "v"}, "adamw_f32": {"p", "m", "v"},
-              "softmax_rows_fwd": {"P", "lse"}, "softmax_rows_bwd": {"dS"}, "lora_dropout": {"t"}}
+              "softmax_rows_fwd": {"P", "lse"}, "softmax_rows_bwd": {"dS"}, "lora_dropout": {"t"},
+              "cfg_ddim_step": {"next_in"}}
 _NOT_KERNELS = {"stream_handle", "workspace", "set_gemm_autotune", "gemm_autotune_cache", "plan_source",
                 "dump_plan_table", "host_layer", "pick_splits", "conv_out_hw", "python_host",
                 "lora_dropout_consts"}

@@ -19,6 +19,11 @@ setup applies (latent - shift_factor) * scaling_factor.
 Kernels: implicit-GEMM convs (stride 2 + one-sided zero padding through the conv gather's range
 check), GroupNorm(+SiLU), fused q|k|v Linear, the materialized single-head attention (512-wide
 head: batched MFMA GEMMs + row softmax), and the quant_conv mean rows as one fp32-out GEMM.
+
+AutoencoderKLDecoder (below) is the decoder half for the training samples (modelSampler/): post_quant_conv, conv_in,
+the same mid block, UpDecoderBlock2D x n (layers_per_block + 1 resnets, nearest-2x Upsample2D through
+conv2d(upsample=True)), GN + SiLU, conv_out 128->3 held as 8 channels.  It is attached to a model only when samples
+are configured.
 """
 from __future__ import annotations
 
@@ -139,18 +144,9 @@ def flops_per_image(cfg: VAEConfig, h: int, w: int) -> float:
     return 2.0 * macs
 
 
-class AutoencoderKLEncoder:
-    """VAE encoder for latent caching; weights in a frozen FlatParamStore (bf16)."""
-
-    def __init__(self, cfg: VAEConfig, device, dtype=BF16, seed: int | None = 0):
-        self.cfg = cfg
-        self.device = torch.device(device)
-        self.specs = vae_encoder_specs(cfg)
-        self.store = FlatParamStore([(n, _store_shape(n, sh, k), "vae") for n, sh, k, _ in self.specs], dtype,
-                                    self.device, trainable=False)
-        self.config = {"scaling_factor": cfg.scaling_factor, "shift_factor": cfg.shift_factor}
-        if seed is not None:
-            self.init_weights(seed)
+class _VAEBlocks:
+    """what the encoder and the decoder share: the frozen flat store's parameter plumbing (a subclass supplies specs,
+    store, `_assign` and `state_dict` for its own layout) and the AutoencoderKL blocks on the HIP kernels."""
 
     # ----- parameters ---------------------------------------------------------------------------
     def init_weights(self, seed: int):
@@ -165,30 +161,12 @@ class AutoencoderKLEncoder:
                 else:
                     self.store.params[name].zero_()
 
-    def _assign(self, name, v, kind):
-        p = self.store.params[name]
-        if kind == "conv":
-            v = v.permute(0, 2, 3, 1) if v.shape[2] > 1 else v.reshape(v.shape[0], v.shape[1])
-            if name == "encoder.conv_in.weight":
-                v = torch.nn.functional.pad(v, (0, PAD_IN - v.shape[-1]))
-        p.data.copy_(v.to(p.dtype))
-
     def num_parameters(self) -> int:
         return sum(math.prod(sh) for _, sh, _, _ in self.specs)
 
-    def state_dict(self, dtype=None):
-        out = {}
-        for name, shape, kind, _ in self.specs:
-            v = self.store.params[name].detach()
-            if kind == "conv":
-                v = v.reshape(v.shape[0], v.shape[1], 1, 1) if v.dim() == 2 else v.permute(0, 3, 1, 2)
-                v = v[:, :shape[1]]
-            out[name] = v.to(dtype or v.dtype).contiguous()
-        return out
-
     def load_state_dict(self, sd):
-        """diffusers AutoencoderKL keys (encoder.* and quant_conv.* when the config has one; decoder keys are
-        ignored)."""
+        """diffusers AutoencoderKL keys: the half this object holds (encoder.* + quant_conv.*, or decoder.* +
+        post_quant_conv.*); the other half's keys are ignored."""
         with torch.no_grad():
             for name, shape, kind, _ in self.specs:
                 if tuple(sd[name].shape) != tuple(shape):
@@ -225,6 +203,38 @@ class AutoencoderKLEncoder:
         out = K.linear(o.view(-1, C), self.W(p + ".to_out.0.weight"), bias=self.W(p + ".to_out.0.bias"),
                        residual=x.view(-1, C))
         return out.view(N, H, W_, C)
+
+
+class AutoencoderKLEncoder(_VAEBlocks):
+    """VAE encoder for latent caching; weights in a frozen FlatParamStore (bf16)."""
+
+    def __init__(self, cfg: VAEConfig, device, dtype=BF16, seed: int | None = 0):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.specs = vae_encoder_specs(cfg)
+        self.store = FlatParamStore([(n, _store_shape(n, sh, k), "vae") for n, sh, k, _ in self.specs], dtype,
+                                    self.device, trainable=False)
+        self.config = {"scaling_factor": cfg.scaling_factor, "shift_factor": cfg.shift_factor}
+        if seed is not None:
+            self.init_weights(seed)
+
+    def _assign(self, name, v, kind):
+        p = self.store.params[name]
+        if kind == "conv":
+            v = v.permute(0, 2, 3, 1) if v.shape[2] > 1 else v.reshape(v.shape[0], v.shape[1])
+            if name == "encoder.conv_in.weight":
+                v = torch.nn.functional.pad(v, (0, PAD_IN - v.shape[-1]))
+        p.data.copy_(v.to(p.dtype))
+
+    def state_dict(self, dtype=None):
+        out = {}
+        for name, shape, kind, _ in self.specs:
+            v = self.store.params[name].detach()
+            if kind == "conv":
+                v = v.reshape(v.shape[0], v.shape[1], 1, 1) if v.dim() == 2 else v.permute(0, 3, 1, 2)
+                v = v[:, :shape[1]]
+            out[name] = v.to(dtype or v.dtype).contiguous()
+        return out
 
     # ----- encode -------------------------------------------------------------------------------
     @torch.no_grad()
@@ -265,3 +275,148 @@ class AutoencoderKLEncoder:
         return self.encode_nhwc(K.image_to_nhwc(images.contiguous(), 2.0, -1.0, PAD_IN))
 
     __call__ = encode
+
+
+# ----- decoder (training samples) ---------------------------------------------------------------
+PAD_OUT = 8   # conv_out output channels held (RGB zero-padded to the store's 8-channel granule)
+
+
+def _pad8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def vae_decoder_specs(cfg: VAEConfig):
+    """(name, diffusers shape, kind, fan_in) of AutoencoderKL's decoder half in execution order: post_quant_conv
+    (when use_quant_conv), decoder.conv_in, the mid block, the up blocks over the reversed block_out_channels
+    (layers_per_block + 1 resnets each, a nearest-2x Upsample2D conv on all but the last), conv_norm_out, conv_out."""
+    ch = cfg.block_out_channels
+    L = cfg.latent_channels
+    s = _conv("post_quant_conv", L, L, 1) if cfg.use_quant_conv else []
+    c = ch[-1]
+    s += _conv("decoder.conv_in", L, c)
+    a = "decoder.mid_block.attentions.0"
+    s += _resnet("decoder.mid_block.resnets.0", c, c)
+    s += _norm(a + ".group_norm", c)
+    s += [(f"{a}.to_{x}.weight", (c, c), "linear", c) for x in "qkv"]
+    s += [(f"{a}.to_{x}.bias", (c,), "bias", c) for x in "qkv"]
+    s += [(a + ".to_out.0.weight", (c, c), "linear", c), (a + ".to_out.0.bias", (c,), "bias", c)]
+    s += _resnet("decoder.mid_block.resnets.1", c, c)
+    cin = c
+    for i, c in enumerate(reversed(ch)):
+        for j in range(cfg.layers_per_block + 1):
+            s += _resnet(f"decoder.up_blocks.{i}.resnets.{j}", cin if j == 0 else c, c)
+        if i < len(ch) - 1:
+            s += _conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", c, c)
+        cin = c
+    s += _norm("decoder.conv_norm_out", ch[0]) + _conv("decoder.conv_out", ch[0], cfg.in_channels)
+    return s
+
+
+def _decoder_store_shape(name, shape, kind, cfg: VAEConfig):
+    """store layout of a decoder parameter: convs [co, kh, kw, ci] (1x1: [co, ci]); the latent side (conv_in's input,
+    post_quant_conv both ways) and conv_out's output channels zero-padded to multiples of 8"""
+    mod = name.rpartition(".")[0]
+    if kind == "conv":
+        co, ci, kh, kw = shape
+        if mod in ("decoder.conv_in", "post_quant_conv"):
+            ci = _pad8(ci)
+        if mod == "post_quant_conv":
+            co = _pad8(co)
+        if mod == "decoder.conv_out":
+            co = PAD_OUT
+        return (co, ci) if kh == 1 else (co, kh, kw, ci)
+    if kind == "bias" and mod == "post_quant_conv":
+        return (_pad8(shape[0]),)
+    if kind == "bias" and mod == "decoder.conv_out":
+        return (PAD_OUT,)
+    return shape
+
+
+def decoder_flops_per_image(cfg: VAEConfig, h: int, w: int) -> float:
+    """analytic decoder FLOPs (2 x MACs; norms / softmax excluded) for an h x w image (latent h/f x w/f)."""
+    ch = cfg.block_out_channels
+    f = 1 << (len(ch) - 1)
+    hw = (h // f) * (w // f)
+    L = cfg.latent_channels
+    c = ch[-1]
+    macs = (hw * L * L if cfg.use_quant_conv else 0) + hw * L * c * 9
+    macs += 2 * (2 * hw * c * c * 9) + 4 * hw * c * c + 2 * hw * hw * c
+    cin = c
+    for i, c in enumerate(reversed(ch)):
+        for j in range(cfg.layers_per_block + 1):
+            ci = cin if j == 0 else c
+            macs += hw * ci * c * 9 + hw * c * c * 9 + (hw * ci * c if ci != c else 0)
+        if i < len(ch) - 1:
+            hw *= 4
+            macs += hw * c * c * 9
+        cin = c
+    macs += hw * ch[0] * cfg.in_channels * 9
+    return 2.0 * macs
+
+
+class AutoencoderKLDecoder(_VAEBlocks):
+    """VAE decoder for training samples: forward only, bf16, its own frozen FlatParamStore.  The blocks are the
+    encoder's (_VAEBlocks: GroupNorm(+SiLU), ResnetBlock2D, the single-head mid attention), plus nearest-2x
+    Upsample2D through conv2d(upsample=True)."""
+
+    def __init__(self, cfg: VAEConfig, device, dtype=BF16, seed: int | None = 0):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.specs = vae_decoder_specs(cfg)
+        self.store = FlatParamStore([(n, _decoder_store_shape(n, sh, k, cfg), "vae") for n, sh, k, _ in self.specs],
+                                    dtype, self.device, trainable=False)
+        self.config = {"scaling_factor": cfg.scaling_factor, "shift_factor": cfg.shift_factor}
+        if seed is not None:
+            self.init_weights(seed)
+
+    def _assign(self, name, v, kind):
+        p = self.store.params[name]
+        if kind == "conv":
+            v = v.permute(0, 2, 3, 1) if v.shape[2] > 1 else v.reshape(v.shape[0], v.shape[1])
+        if tuple(v.shape) != tuple(p.shape):   # a zero-padded parameter: the value fills the leading corner
+            p.data.zero_()
+            p.data[tuple(slice(0, n) for n in v.shape)].copy_(v.to(p.dtype))
+        else:
+            p.data.copy_(v.to(p.dtype))
+
+    def state_dict(self, dtype=None):
+        out = {}
+        for name, shape, kind, _ in self.specs:
+            v = self.store.params[name].detach()
+            if kind == "conv":
+                v = v.reshape(v.shape[0], v.shape[1], 1, 1) if v.dim() == 2 else v.permute(0, 3, 1, 2)
+            v = v[tuple(slice(0, n) for n in shape)]
+            out[name] = v.to(dtype or v.dtype).contiguous()
+        return out
+
+    @torch.no_grad()
+    def decode(self, latent):
+        """latent: [B, h, w, L] NHWC (fp32 or bf16), scaled as the UNet sees it -> image bf16 NHWC [B, 8h', 8w', 8]
+        in [-1, 1] nominally, channels >= 3 zero (AutoencoderKL.decode(latent / scaling_factor), with FLUX's
+        shift_factor added back)."""
+        cfg = self.cfg
+        ch = cfg.block_out_channels
+        L = cfg.latent_channels
+        K._req(latent.dim() == 4 and latent.shape[-1] == L and latent.is_cuda, "latent: cuda NHWC [B, h, w, L]")
+        z = latent.float() / cfg.scaling_factor
+        if cfg.shift_factor:
+            z = z + cfg.shift_factor
+        x = torch.nn.functional.pad(z, (0, _pad8(L) - L)).to(BF16).contiguous()
+        B, H, W_, Lp = x.shape
+        if cfg.use_quant_conv:
+            x = K.linear(x.view(-1, Lp), self.W("post_quant_conv.weight"),
+                         bias=self.W("post_quant_conv.bias")).view(B, H, W_, Lp)
+        h = K.conv2d(x, self.W("decoder.conv_in.weight"), bias=self.W("decoder.conv_in.bias"))
+        h = self._resnet(h, "decoder.mid_block.resnets.0")
+        h = self._attention(h, "decoder.mid_block.attentions.0")
+        h = self._resnet(h, "decoder.mid_block.resnets.1")
+        for i in range(len(ch)):
+            for j in range(cfg.layers_per_block + 1):
+                h = self._resnet(h, f"decoder.up_blocks.{i}.resnets.{j}")
+            if i < len(ch) - 1:
+                p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
+                h = K.conv2d(h, self.W(p + ".weight"), bias=self.W(p + ".bias"), upsample=True)
+        h = self._gn(h, "decoder.conv_norm_out", True)
+        return K.conv2d(h, self.W("decoder.conv_out.weight"), bias=self.W("decoder.conv_out.bias"))
+
+    __call__ = decode

@@ -52,7 +52,11 @@ class GenericTrainer(TimedActionMixin):
         self.one_step_trained = False
         self._has_gradient = False
         self._wallclock_timers = False
-        self._det_flags = 0                # backup / save raised by STEP / EPOCH timers under DP (_raise_timed)
+        self._det_flags = 0                # backup / save / sample raised by STEP / EPOCH timers under DP (_raise_timed)
+        self.model_sampler = None          # modelSampler.StableDiffusionSampler, built by start() (None: FLUX)
+        self.sample_configs: list = []     # the run's sample definitions (util/config/SampleConfig.py)
+        self.sample_prompt_states = None   # ready text states for every sample (callers without tokenizers, tests)
+        self.sample_paths: list[str] = []  # files written so far (rank 0)
         self._ctl_group = None
         self.agreements = 0
         self.rank, self.world = 0, 1
@@ -71,6 +75,7 @@ class GenericTrainer(TimedActionMixin):
         want_data = self.data_loader is None and (cache_ready(cfg) or has_concepts(cfg))
         if want_data and not cache_ready(cfg):   # the model loader fills the caching encoders
             attach_cache_encoders(self.model, cfg, self.device)
+        self._setup_sampling()                   # ... and the VAE decoder, only when samples are configured
         self._load_weights()
         if want_data:
             self.data_loader = create_data_loader(cfg, self.model, self.device, self.rank, self.world)
@@ -124,6 +129,142 @@ class GenericTrainer(TimedActionMixin):
         if hasattr(opt, "train"):
             opt.train()
             self._refresh_derived()
+
+    # ----- training samples ---------------------------------------------------------------------
+    def _setup_sampling(self):
+        """before the weights load: read and check the sample definitions (an unsupported one is refused here, by
+        name), build the sampler, and -- only when there is something to sample -- attach the VAE decoder and keep
+        the text encoders, so the loader fills them with the base weights.  Runs without samples load and hold
+        exactly what they did."""
+        from ..modelSampler import create_model_sampler
+        from ..util.config.SampleConfig import read_sample_configs
+        cfg = self.config
+        if create.is_flux(cfg.model_type):
+            if getattr(cfg, "samples", None) or self.commands.has_sample_commands():
+                print("FLUX: training samples are not built, no samples will be written", flush=True)
+            return
+        self.sample_configs = read_sample_configs(cfg)
+        self.model_sampler = create_model_sampler(cfg.model_type, self.model, self.device)
+        if self.model_sampler is not None:
+            self.model_sampler.base_model_name = getattr(cfg, "base_model_name", "") or ""
+        if self.rank == 0 and any(s.enabled for s in self.sample_configs):   # only rank 0 ever samples
+            self._attach_sample_modules(load=False)
+
+    def _attach_sample_modules(self, load: bool):
+        """the VAE decoder (and, when the checkpoint has tokenizers, the text encoders) on the model; `load` fills
+        a decoder attached after the weights were loaded (a sample command in a run without configured samples)"""
+        import os
+
+        from ..module import vae as V
+        cfg, m = self.config, self.model
+        # the frozen sampling modules always come from the run's own base / VAE model, also when the UNet is
+        # continued from a backup directory, which holds neither (modelLoader frozen_source)
+        m.sampling_source = cfg.model_names()
+        if getattr(m, "vae_decoder", None) is None:
+            vcfg = getattr(m, "vae_config", None) or (V.sd15_vae_config() if create.is_sd15(cfg.model_type)
+                                                      else V.sdxl_vae_config())
+            m.vae_decoder = V.AutoencoderKLDecoder(vcfg, self.device, seed=0)
+            names = cfg.model_names()
+            if load and (names.base_model or names.vae_model):
+                from ..modelLoader.StableDiffusionModelLoader import load_vae_decoder
+                load_vae_decoder(m.vae_decoder, names.vae_model or names.base_model)
+        base = getattr(cfg, "base_model_name", "") or ""
+        if self.sample_prompt_states is None and os.path.isdir(os.path.join(base, "tokenizer")):
+            from ..module import text_encoder as TE
+            sdxl = not create.is_sd15(cfg.model_type)
+            fresh = getattr(m, "text_encoder_1", None) is None
+            if fresh:
+                m.text_encoder_1 = TE.CLIPTextEncoder(TE.clip_l_config(), self.device)
+                if sdxl:
+                    m.text_encoder_2 = TE.CLIPTextEncoder(TE.clip_bigg_config(), self.device)
+            m.keep_text_encoders = True   # dataLoader/create.create_data_loader frees them otherwise
+            if load and fresh and os.path.isdir(base):
+                from ..modelLoader.StableDiffusionModelLoader import load_text_encoders
+                load_text_encoders(m, base)
+
+    def _needs_sample(self, tp) -> bool:
+        """GenericTrainer.py:499-504"""
+        cfg = self.config
+        if not any(s.enabled for s in self.sample_configs):
+            return False
+        return (self.single_action_elapsed("sample_skip_first", cfg.sample_skip_first, cfg.sample_after_unit, tp)
+                and self.repeating_action_needed("sample", cfg.sample_after, cfg.sample_after_unit, tp))
+
+    def sample(self, train_progress: TrainProgress | None = None, sample_params: list | None = None) -> list[str]:
+        """__sample_during_training (GenericTrainer.py:262-318): the configured samples (or the custom ones of a
+        sample_custom command) from the averaged weights -- a schedule-free optimizer's x, the EMA shadow -- and,
+        with an EMA and non_ema_sampling, again from the trained weights into `<i> - <prompt> - no-ema`.  Rank 0
+        samples; the other ranks go on to the next collective.  Runs at an update boundary, outside any captured
+        step graph, and leaves the store, the gradients and the training RNG streams as it found them."""
+        import os
+        import traceback
+        from datetime import datetime
+
+        from ..util.config.SampleConfig import as_sample_config, safe_filename
+        cfg, model = self.config, self.model
+        tp = train_progress or model.train_progress
+        custom = bool(sample_params)
+        if self.model_sampler is None:
+            return []
+        if custom:   # sent mid-run (a UI): one this build cannot draw is named in a log line and skipped
+            configs = []
+            for s in sample_params:
+                try:
+                    configs.append(as_sample_config(s).check_supported())
+                except (NotImplementedError, ValueError, TypeError) as e:
+                    print(f"sample_custom skipped: {e}", flush=True)
+        else:
+            configs = self.sample_configs
+        if self.rank != 0 or not any(s.enabled for s in configs):
+            return []
+        self._attach_sample_modules(load=True)
+        written: list[str] = []
+
+        def loop(postfix: str):
+            for i, sc in enumerate(configs):
+                if not sc.enabled:
+                    continue
+                try:
+                    prompt = safe_filename(sc.prompt)
+                    sub = "custom" if custom else f"{i} - {prompt}{postfix}"
+                    dest = os.path.join(cfg.workspace_dir, "samples", sub,
+                                        f"{cfg.save_filename_prefix}{datetime.now().strftime('%Y-%m-%d_%H-%M-%S')}"
+                                        f"-training-sample-{tp.filename_string()}")
+                    sc = as_sample_config(sc.to_dict()).from_train_config(cfg)
+
+                    def on_sample(image, _i=i, _prompt=prompt):
+                        if (not custom and cfg.samples_to_tensorboard and self.tensorboard is not None
+                                and hasattr(self.tensorboard, "add_image")):
+                            self.tensorboard.add_image(f"sample{_i} - {_prompt}", image, tp.global_step)
+                        cb = getattr(self.callbacks, "on_sample_custom" if custom else "on_sample_default", None)
+                        if cb is not None:
+                            cb(image)
+
+                    written.append(self.model_sampler.sample(sc, dest, cfg.sample_image_format,
+                                                             prompt_states=self.sample_prompt_states,
+                                                             on_sample=on_sample))
+                except Exception:
+                    traceback.print_exc()
+                    print("Error during sampling, proceeding without sampling")
+
+        self._before_eval()
+        ema = getattr(model, "ema", None)
+        try:
+            if ema is not None:
+                ema.copy_ema_to(store_temp=True)
+                self._refresh_derived()
+            loop("")
+        finally:
+            if ema is not None:
+                ema.copy_temp_to()
+                self._refresh_derived()
+        try:
+            if ema is not None and not custom and cfg.non_ema_sampling:
+                loop(" - no-ema")
+        finally:
+            self._after_eval()
+        self.sample_paths += written
+        return written
 
     def _attach_norm_overlap(self):
         """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor, CAME, Prodigy): clip_grad_norm_'s norm pass runs during backward
@@ -356,8 +497,10 @@ class GenericTrainer(TimedActionMixin):
             self._det_flags |= kind
         elif kind == 1:
             self.commands.backup()
-        else:
+        elif kind == 2:
             self.commands.save()
+        else:
+            self.commands.sample_default()
 
     def _agree(self, flags: int, step: int) -> int:
         """Ranks must take a backup / save together (both barrier).  A wall-clock timer can fire on one
@@ -382,7 +525,9 @@ class GenericTrainer(TimedActionMixin):
         if self.data_loader is None:
             raise RuntimeError("no data: set cache_dir to a latent cache or configure concepts")
         self._wallclock_timers = any(TimedActionMixin._unit(u) in ("SECOND", "MINUTE", "HOUR")
-                                     for u in (cfg.backup_after_unit, cfg.save_every_unit))
+                                     for u in (cfg.backup_after_unit, cfg.save_every_unit)
+                                     + ((cfg.sample_after_unit,) if any(s.enabled for s in self.sample_configs)
+                                        else ()))
         steps = 0
         # losses are read from the device every `flush_every` steps: printed when log_every is set, written as
         # the loss scalars either way (the reference logs them every update step, GenericTrainer.py:723-733)
@@ -400,6 +545,8 @@ class GenericTrainer(TimedActionMixin):
                         self._raise_timed(1, cfg.backup_after_unit)
                     if self._needs_save(tp):
                         self._raise_timed(2, cfg.save_every_unit)
+                    if self._needs_sample(tp):
+                        self._raise_timed(4, cfg.sample_after_unit)
                     if not self._has_gradient:
                         self._run_commands(tp, self._agreement_point(tp))
                     gs, update = tp.global_step, self._is_update_step(tp)
@@ -443,13 +590,23 @@ class GenericTrainer(TimedActionMixin):
             gc.enable()
 
     def _run_commands(self, tp, agreement: bool):
-        """at an update boundary (no accumulated gradient pending): the backup / save the timers or the command
-        object asked for (GenericTrainer.py:653-668); sticky commands only at an agreement point"""
+        """at an update boundary (no accumulated gradient pending): the samples / backup / save the timers or the
+        command object asked for (GenericTrainer.py:629-668); sticky commands only at an agreement point"""
         flags, self._det_flags = self._det_flags, 0
+        custom = []
         if agreement:
+            custom = self.commands.get_and_reset_sample_custom_commands()
             sticky = (int(self.commands.get_and_reset_backup_command())
-                      | int(self.commands.get_and_reset_save_command()) << 1)
+                      | int(self.commands.get_and_reset_save_command()) << 1
+                      | int(self.commands.get_and_reset_sample_default_command()) << 2
+                      | int(bool(custom)) << 3)
             flags |= self._agree(sticky, tp.global_step)
+        # a sample raised by a STEP / EPOCH timer (a deterministic flag) runs at its exact step like backup and save;
+        # only the sticky sample commands wait for the agreement point
+        if flags & 4:   # GenericTrainer.py:629-654: samples first, then backup / save
+            self.sample(tp)
+        if flags & 8 and custom:   # rank 0's commands decide (_agree); it holds the list
+            self.sample(tp, custom)
         if flags & 1:
             self.backup(tp)
         if flags & 2:

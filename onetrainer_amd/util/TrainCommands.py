@@ -2,8 +2,8 @@
 
 The train loop polls them between steps: stop (checked after every step and epoch), backup and
 save (executed at the next optimizer-update boundary, GenericTrainer.py:653-668).  The sample
-commands are accepted and dropped: sampling is outside this build's hot path.  `reset()` keeps a
-pending stop, as the reference does.
+commands are executed at the same boundary (GenericTrainer.sample: SD 1.5 and SDXL; a FLUX run
+logs one line and writes none).  `reset()` keeps a pending stop, as the reference does.
 """
 from __future__ import annotations
 
@@ -64,6 +64,9 @@ class TrainCommands:
     def sample_custom(self, sample_params):
         self._sample_custom.append(sample_params)
         self._notify()
+
+    def has_sample_commands(self) -> bool:
+        return self._flags["sample_default"] or bool(self._sample_custom)
 
     def get_and_reset_sample_custom_commands(self) -> list:
         out, self._sample_custom = self._sample_custom, []

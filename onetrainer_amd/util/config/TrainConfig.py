@@ -153,6 +153,18 @@ class TrainConfig:
     save_every_unit: str = "NEVER"
     save_skip_first: int = 0
     save_filename_prefix: str = ""
+    # training samples (TrainConfig.py:969-978; util/config/SampleConfig.py): inline list of SampleConfig dicts,
+    # else the sample definition file (a missing file: no samples)
+    samples: list | None = None
+    sample_definition_file_name: str = "training_samples/samples.json"
+    sample_after: float = 10
+    sample_after_unit: str = "MINUTE"
+    sample_skip_first: int = 0
+    sample_image_format: str = "JPG"
+    samples_to_tensorboard: bool = True
+    non_ema_sampling: bool = True
+    text_encoder_layer_skip: int = 0          # TrainConfig.py:873,883
+    text_encoder_2_layer_skip: int = 0
     # concepts (TrainConfig.py:793-794): inline list of ConceptConfig dicts, else the concept file
     concepts: list | None = None
     concept_file_name: str = "training_concepts/concepts.json"

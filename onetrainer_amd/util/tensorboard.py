@@ -36,6 +36,21 @@ class ScalarLog:
         if self.enabled:
             self.pending.append((tag, value, int(step), time.time()))
 
+    def add_image(self, tag: str, image, step: int):
+        """a training sample (PIL image or HWC uint8 array): written only when tensorboard is installed (the JSON
+        lines hold scalars alone); without it nothing is opened, so a run that logs nothing still leaves no files"""
+        if not self.enabled:
+            return
+        if self._file is None:
+            try:
+                import torch.utils.tensorboard  # noqa: F401
+            except Exception:
+                return
+            self._open()
+        if self._writer is not None:
+            import numpy as np
+            self._writer.add_image(tag, np.asarray(image), int(step), dataformats="HWC")
+
     def flush(self):
         if not self.enabled or not self.pending:
             return
