@@ -428,6 +428,11 @@ int otamd_lora_shadow_entry_size(void);
    (all ranks) tensor that row 0 of t is.  site_id in [0, 2^24), (row0 + M) * Wq <= 2^40. */
 int otamd_lora_dropout(void* t, long long M, int width, const unsigned long long* seed, int site_id, long long row0,
     unsigned long long thr, float scale, hipStream_t s);
+/* the same mask with per-sample row numbering (the validation pass): row m of t counts as row m % rows_per of its
+   sample (rows_per > 0: rows of one sample, sample-major rows) or row m / -rows_per (rows_per < 0: minus the batch
+   size, token-major rows r = t * B + b), so every sample gets the mask of a batch of one on rank 0 */
+int otamd_lora_dropout_per_sample(void* t, long long M, int width, const unsigned long long* seed, int site_id,
+    long long rows_per, unsigned long long thr, float scale, hipStream_t s);
 
 /* replaces: DoRAModule.forward's weight expression (modules/module/LoRAModule.py:385-412) for every adapted module in
    one launch: n = ||W + s up down|| over every axis but the kept one (axis 0: input channels, 1: output channels)
@@ -486,6 +491,12 @@ int otamd_noise(void* out, int f32, long long n, long long offset, unsigned long
    dtype in the reference's order.  NHWC tensor, hwc = h * w * C; offset = global element index of out[0]. */
 int otamd_noise_ex(void* out, int f32, long long n, long long offset, unsigned long long seed, int C,
     long long hwc, float offset_weight, float perturbation_weight, hipStream_t s);
+/* the deterministic noise of the validation pass: out = a whole number of NHWC samples of hwc elements, each the
+   noise (offset / perturbation terms included) of a batch of one at offset 0, so a sample's noise does not depend
+   on the batch or rank it is drawn in (the reference validates at batch size 1 with seed 0,
+   modules/trainer/GenericTrainer.py:319-389) */
+int otamd_noise_per_sample(void* out, int f32, long long n, unsigned long long seed, int C, long long hwc,
+    float offset_weight, float perturbation_weight, hipStream_t s);
 /* test hook: raw standard-normal draws of Philox stream `stream_id` (1 = noise, 4 = offset, 5 = perturbation) */
 int otamd_noise_stream(void* out, int f32, long long n, long long offset, unsigned long long seed, int stream_id,
     hipStream_t s);
@@ -541,6 +552,15 @@ int otamd_diffusion_loss(const void* pred, int cpad, const void* target, int tgt
     int normalize, float scale, const float* loss_weight, const int* timestep, const float* sqrt_acp,
     const float* sqrt_1m, int loss_fn, float gamma, int v_pred, int num_t, float ga, float* ws, long long ws_floats,
     float* loss_out, float* coef, float* losses_out, hipStream_t s);
+
+/* replaces: the host side of the reference's validation loop (modules/trainer/GenericTrainer.py:319-389:
+   loss.item() per image, then a per-concept mean): adds the per-sample losses (losses_out above) of one batch and
+   a count of 1 each into acc[concept_index[b]] = (sum, count), double [n_concepts][2] on the device.  One
+   workgroup, no atomics, samples in ascending b, in double: equal to a sequential float64 sum on the host.
+   concept_index_host (nullable): the same indices in host memory; one outside [0, n_concepts) is EINVAL before
+   launch.  The kernel skips such a sample either way.  B <= 1024. */
+int otamd_validation_accumulate(const float* losses, const int* concept_index, const int* concept_index_host, int B,
+    int n_concepts, double* acc, hipStream_t s);
 
 /* replaces: autograd of the loss above: dpred = m (2 d coef[b,0] + sign(d) coef[b,1] + tanh(d) coef[b,2]) grad_out[0],
    bf16, pad channels 0 */

@@ -247,6 +247,7 @@ SIGNATURES: dict[str, list] = {
     "otamd_lora_shadow_entry_size": [],
     # lora_dropout.hip
     "otamd_lora_dropout": [VP, LL, I, VP, I, LL, U64, F, VP],
+    "otamd_lora_dropout_per_sample": [VP, LL, I, VP, I, LL, U64, F, VP],
     # dora.hip
     "otamd_dora_merge": [VP, VP, I, I, F, VP, LL, VP, LL, VP, LL, VP, LL, VP],
     "otamd_dora_project": [VP, VP, I, I, I, I, VP, LL, VP, VP, LL, VP, LL, VP, LL, I, VP],
@@ -278,6 +279,7 @@ SIGNATURES: dict[str, list] = {
     # diffusion.hip
     "otamd_noise": [VP, I, LL, LL, U64, VP],
     "otamd_noise_ex": [VP, I, LL, LL, U64, I, LL, F, F, VP],
+    "otamd_noise_per_sample": [VP, I, LL, U64, I, LL, F, F, VP],
     "otamd_noise_stream": [VP, I, LL, LL, U64, I, VP],
     "otamd_timesteps": [VP, I, LL, U64, I, I, I, I, F, F, F, VP, VP],
     "otamd_timesteps_ex": [VP, I, LL, U64, I, I, I, I, F, F, F, VP, VP, I, VP],
@@ -288,6 +290,8 @@ SIGNATURES: dict[str, list] = {
     "otamd_diffusion_loss": [VP, I, VP, I, VP, I, LL, I, F, F, F, F, I, F, VP, VP, VP, VP, I, F, I, I, F, VP, LL, VP,
                              VP, VP, VP],
     "otamd_diffusion_loss_grad": [VP, I, VP, I, VP, I, LL, I, F, VP, VP, VP, VP],
+    # validation.hip
+    "otamd_validation_accumulate": [VP, VP, VP, I, I, VP, VP],
     # sampler.hip
     "otamd_cfg_ddim_step": [VP, VP, VP, VP, I, LL, F, F, I, VP, VP, I, I, I, VP, LL, VP],
     "otamd_cfg_ddim_step_ws_bytes": [I, LL],

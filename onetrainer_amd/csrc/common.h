@@ -130,6 +130,10 @@ __device__ __forceinline__ uint32_t sr_bits(uint32_t k, uint64_t idx) {
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// the largest batch the one-workgroup loss finalize kernels (diffusion.hip) and the validation accumulate
+// (validation.hip) take: their per-sample values are staged in LDS
+#define LOSS_MAX_B 1024
+
 #define OTAMD_CHECK_LAUNCH()                              \
   do {                                                    \
     if (hipGetLastError() != hipSuccess) return OTAMD_ELAUNCH; \

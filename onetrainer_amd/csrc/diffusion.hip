@@ -53,10 +53,12 @@ __global__ void noise_kernel(void* out, int f32, long long n, long long offset, 
 //   noise = noise + pw * N_5 (perturbation noise), each op rounded to the tensor dtype in the reference's
 //   order (python-float x tensor, then tensor + tensor).  NHWC [.., hw, C] layout: element g of the global
 //   tensor is sample g / hwc, channel g % C.  Stream 4 is indexed by sample * C + c, stream 5 like stream 1.
+// restart (the validation pass): every sample restarts the counters at 0, g = i % hwc, so sample b of a batch gets
+//   the noise it would get as a batch of one on rank 0, whatever the batch size or rank.
 __global__ void noise_ex_kernel(void* out, int f32, long long n, long long offset, unsigned long long seed, int C,
-                                long long hwc, float ow, float pw) {
+                                long long hwc, float ow, float pw, int restart) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const long long g = offset + i;
+    const long long g = restart ? i % hwc : offset + i;
     float v = round_t(philox_normal(seed, 1u, (uint64_t)g), f32);
     if (ow > 0.f) {
       const float o = round_t(philox_normal(seed, 4u, (uint64_t)((g / hwc) * C + g % C)), f32);
@@ -260,7 +262,6 @@ __device__ __forceinline__ float timestep_weighted(float w, int b, int loss_fn, 
 // loss_fn: 0 constant, 1 min-snr-gamma, 2 debiased estimation, 3 p2 (ModelSetupDiffusionLossMixin.py:170-225),
 // 4 sigma = (t + 1) / num_t (flow matching, :226-231,297-300,317-319).  The per-sample losses are
 // summed in sample order by one lane (deterministic, like the reference's .mean()).
-#define LOSS_MAX_B 1024
 __global__ void mse_finalize_kernel(const float* partial, int nblk, int B, long long per, float mse_strength,
                                     float scale, const float* loss_weight, const int* timestep, const float* sqrt_acp,
                                     const float* sqrt_1m, int loss_fn, float gamma, int v_pred, int num_t, float ga,
@@ -433,7 +434,19 @@ OTAMD_API int otamd_noise_ex(void* out, int f32, long long n, long long offset, 
       !(perturbation_weight >= 0.f))
     return OTAMD_EINVAL;
   if (n == 0) return OTAMD_OK;
-  noise_ex_kernel<<<gfor(n), 256, 0, s>>>(out, f32, n, offset, seed, C, hwc, offset_weight, perturbation_weight);
+  noise_ex_kernel<<<gfor(n), 256, 0, s>>>(out, f32, n, offset, seed, C, hwc, offset_weight, perturbation_weight, 0);
+  OTAMD_CHECK_LAUNCH();
+  return OTAMD_OK;
+}
+// out: [n] = a whole number of NHWC samples of hwc elements; every sample is the noise of a batch of one at
+// offset 0 (the offset / perturbation terms included): the deterministic inputs of the validation pass
+OTAMD_API int otamd_noise_per_sample(void* out, int f32, long long n, unsigned long long seed, int C, long long hwc,
+                                     float offset_weight, float perturbation_weight, hipStream_t s) {
+  if (!out || n < 0 || C <= 0 || hwc <= 0 || hwc % C || n % hwc || !(offset_weight >= 0.f) ||
+      !(perturbation_weight >= 0.f))
+    return OTAMD_EINVAL;
+  if (n == 0) return OTAMD_OK;
+  noise_ex_kernel<<<gfor(n), 256, 0, s>>>(out, f32, n, 0, seed, C, hwc, offset_weight, perturbation_weight, 1);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

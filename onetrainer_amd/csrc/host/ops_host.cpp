@@ -635,6 +635,33 @@ Tensor geglu_bwd(const Tensor& h, const Tensor& dout, int64_t stream) {
   return dh;
 }
 
+// ---- validation pass: per-concept (sum, count) of a batch's per-sample losses, on the device ----
+// kernels.validation_accumulate: index_host (optional, CPU int32 [B]) lets the launcher refuse an index outside
+// [0, n_concepts) before anything is queued
+void validation_accumulate(const Tensor& losses, const Tensor& concept_index, int64_t n_concepts, const Tensor& acc,
+                           const optional<Tensor>& index_host, int64_t stream) {
+  req(losses.is_cuda() && is_f32(losses) && losses.dim() == 1 && losses.is_contiguous() && losses.numel() >= 1 &&
+          losses.numel() <= 1024,
+      "validation_accumulate losses: contiguous f32 cuda [B], 1 <= B <= 1024");
+  const int64_t B = losses.numel();
+  req(concept_index.scalar_type() == at::kInt && concept_index.is_contiguous() && concept_index.numel() == B &&
+          concept_index.device() == losses.device(),
+      "validation_accumulate concept_index: contiguous int32 [B] on the losses' device");
+  req(n_concepts >= 1 && acc.scalar_type() == at::kDouble && acc.is_contiguous() && acc.numel() == 2 * n_concepts &&
+          acc.device() == losses.device(),
+      "validation_accumulate acc: contiguous f64 [n_concepts, 2] on the losses' device");
+  const int* host = nullptr;
+  if (index_host.has_value()) {
+    req(!index_host->is_cuda() && index_host->scalar_type() == at::kInt && index_host->is_contiguous() &&
+            index_host->numel() == B,
+        "validation_accumulate index_host: contiguous CPU int32 [B]");
+    host = index_host->data_ptr<int>();
+  }
+  check(otamd_validation_accumulate((const float*)P(losses), (const int*)P(concept_index), host, (int)B,
+                                    (int)n_concepts, (double*)P(acc), S(stream)),
+        "otamd_validation_accumulate");
+}
+
 void clear_workspaces() {
   std::lock_guard<std::mutex> lk(g_ws_mu);
   g_ws.clear();
@@ -667,6 +694,7 @@ PYBIND11_MODULE(_otamd_host, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("geglu_fwd", &geglu_fwd);
   m.def("geglu_bwd", &geglu_bwd);
+  m.def("validation_accumulate", &validation_accumulate);
   m.def("clear_workspaces", &clear_workspaces);
   m.def("gemm_args_size", []() { return (int64_t)sizeof(GemmArgs); });
   m.def("attn_args_size", []() { return (int64_t)sizeof(AttnArgs); });

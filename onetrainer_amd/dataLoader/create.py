@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from ..util.config.plain import plain
+from ..util.config.plain import plain, value
 from .latent_cache import INDEX, LatentCacheDataLoader, LatentCacheWriter, default_bucketing
 
 IMAGE_EXT = (".png", ".jpg", ".jpeg", ".webp", ".bmp", ".tif", ".tiff")
@@ -62,7 +62,29 @@ def attach_cache_encoders(model, config, device) -> None:
         model.text_encoder_2 = TE.T5TextEncoder(TE.t5_xxl_config(), device)
 
 
-def _concepts(cfg) -> list:
+VALIDATION_DIR = "validation"   # the held-out set's own latent cache: <cache_dir>/validation
+
+
+def validation_cache_dir(config) -> str:
+    return os.path.join(plain(config).cache_dir, VALIDATION_DIR)
+
+
+def validation_cache_ready(config) -> bool:
+    return os.path.isfile(os.path.join(validation_cache_dir(config), INDEX))
+
+
+def is_validation_concept(concept: dict) -> bool:
+    """ConceptConfig.type == VALIDATION, or the legacy key `validation_concept` that the reference migrates to it
+    (modules/util/config/ConceptConfig.py:167-168)"""
+    t = concept.get("type")
+    if t is not None:
+        return str(value(t)) == "VALIDATION"
+    return bool(concept.get("validation_concept", False))
+
+
+def _concepts(cfg, validation: bool = False) -> list:
+    """the enabled concepts of one side of the split (DataLoaderMgdsMixin.py:29-30: the validation concepts or all
+    the others); the split applies whether or not `validation` is on, so a held-out image is never trained on"""
     concepts = cfg.concepts
     if not concepts:
         path = cfg.concept_file_name
@@ -73,9 +95,41 @@ def _concepts(cfg) -> list:
     out = []
     for c in concepts:
         c = c.to_dict() if hasattr(c, "to_dict") else dict(c)
-        if c.get("enabled", True):
+        if c.get("enabled", True) and is_validation_concept(c) == validation:
             out.append(c)
     return out
+
+
+def validation_concepts(config) -> list[dict]:
+    """{name, path, seed} of every enabled validation concept; a sample's concept index is its position here.
+    Without concepts configured (a run on a ready cache) there are none."""
+    cfg = plain(config)
+    if not has_concepts(cfg):
+        return []
+    return [{"name": c.get("name", "") or "", "path": c.get("path", ""), "seed": int(c.get("seed", 0) or 0)}
+            for c in _concepts(cfg, validation=True)]
+
+
+def validation_labels(concepts: list[dict]) -> list[str]:
+    """the scalar label of every validation concept (GenericTrainer.py:358-370): its name, else the basename of its
+    path; a label already taken by a concept of another seed gets the suffix (1), (2), ...; concepts of one seed
+    share the first one's label (the reference accumulates by seed).  Concepts are visited in index order."""
+    seed_to_label: dict = {}
+    label_to_seed: dict = {}
+    for c in concepts:
+        seed = c["seed"]
+        label = c["name"] if c["name"] else os.path.basename(c["path"])
+        if label in label_to_seed and label_to_seed[label] != seed:
+            suffix = 1
+            new = f"{label}({suffix})"
+            while new in label_to_seed and label_to_seed[new] != seed:
+                suffix += 1
+                new = f"{label}({suffix})"
+            label = new
+        if seed not in seed_to_label:
+            seed_to_label[seed] = label
+            label_to_seed[label] = seed
+    return [seed_to_label[c["seed"]] for c in concepts]
 
 
 def _caption(img_path: str, concept: dict) -> str:
@@ -108,12 +162,28 @@ def mask_path(img_path: str) -> str | None:
 
 
 def enumerate_samples(config) -> list[tuple]:
-    """(image path, caption) for every enabled concept (mgds CollectPaths + caption loading); under
-    masked_training (image path, caption, mask path or None).  A -masklabel.png is never listed as an image."""
+    """(image path, caption) for every enabled training (non-validation) concept (mgds CollectPaths + caption
+    loading); under masked_training (image path, caption, mask path or None).  A -masklabel.png is never listed as
+    an image."""
     cfg = plain(config)
+    return [s for s, _ in _enumerate(cfg, _concepts(cfg))]
+
+
+def enumerate_validation_samples(config) -> list[dict]:
+    """the held-out set: for every image of every enabled validation concept {"sample": the tuple
+    enumerate_samples gives, "concept_index": the concept's position among the enabled validation concepts,
+    "name" / "path" / "seed": the concept's}"""
+    cfg = plain(config)
+    concepts = validation_concepts(cfg)
+    return [{"sample": s, "concept_index": i, **concepts[i]}
+            for s, i in _enumerate(cfg, _concepts(cfg, validation=True))]
+
+
+def _enumerate(cfg, concepts: list) -> list[tuple]:
+    """(sample tuple, position of its concept in `concepts`)"""
     masked = bool(getattr(cfg, "masked_training", False))
     out = []
-    for c in _concepts(cfg):
+    for ci, c in enumerate(concepts):
         if masked:
             on = [k for k in MASK_AUGMENTATIONS if (c.get("image") or {}).get(k)]
             if on:
@@ -125,7 +195,7 @@ def enumerate_samples(config) -> list[tuple]:
             for fn in sorted(files):
                 if fn.lower().endswith(IMAGE_EXT) and not fn.lower().endswith(MASK_POSTFIX):
                     p = os.path.join(d, fn)
-                    out.append((p, _caption(p, c), mask_path(p)) if masked else (p, _caption(p, c)))
+                    out.append(((p, _caption(p, c), mask_path(p)) if masked else (p, _caption(p, c)), ci))
     return out
 
 
@@ -142,15 +212,24 @@ def _tokenizers(cfg):
     return toks
 
 
-def build_cache(config, model, device, rank: int = 0) -> int:
+def build_cache(config, model, device, rank: int = 0, validation: bool = False) -> int:
+    """the training set into cache_dir, or (validation) the held-out set into <cache_dir>/validation with every
+    index entry carrying its concept index and the index the concepts' name / path / seed"""
     from PIL import Image
 
     from ..module import text_encoder as TE
     cfg = plain(config)
     fam = _family(cfg.model_type)
-    samples = enumerate_samples(cfg)
+    concept_of = None
+    if validation:
+        held_out = enumerate_validation_samples(cfg)
+        samples = [v["sample"] for v in held_out]
+        concept_of = [v["concept_index"] for v in held_out]
+    else:
+        samples = enumerate_samples(cfg)
     if not samples:
-        raise FileNotFoundError("no training images found in the configured concepts")
+        raise FileNotFoundError(f"no {'validation' if validation else 'training'} images found in the configured "
+                                "concepts")
     toks = _tokenizers(cfg)
 
     def ids(tok, caption):
@@ -172,18 +251,43 @@ def build_cache(config, model, device, rank: int = 0) -> int:
         rows = (row(s, {"tokens_1": ids(toks[0], s[1])}) for s in samples)
     # a generator: each file is opened (and, once decoded, closed) inside the writer's loop, so a concept
     # folder larger than the open-file limit caches
-    writer = LatentCacheWriter(lambda im: model.vae_encoder.encode(im), cfg.cache_dir, default_bucketing(cfg),
-                               device, rank=rank, text_fn=text_fn)
+    if validation:
+        rows = ({**r, "concept_index": ci} for r, ci in zip(rows, concept_of))
+    writer = LatentCacheWriter(lambda im: model.vae_encoder.encode(im),
+                               validation_cache_dir(cfg) if validation else cfg.cache_dir, default_bucketing(cfg),
+                               device, rank=rank, text_fn=text_fn,
+                               concepts=validation_concepts(cfg) if validation else None)
     return writer.write(rows)
+
+
+def validation_cache_needed(config) -> bool:
+    """`validation` is on, the concepts hold at least one validation concept, and its cache is not written yet"""
+    cfg = plain(config)
+    return bool(getattr(cfg, "validation", False)) and not validation_cache_ready(cfg) and bool(validation_concepts(cfg))
+
+
+def create_validation_data_loader(config, device, rank: int = 0, world: int = 1):
+    """the held-out set's loader (create_data_loader builds its cache beside the training one), or None when
+    `validation` is off or there is no validation concept: the pass is then skipped, as the reference returns early
+    on an empty loader (GenericTrainer.py:324-325)"""
+    cfg = plain(config)
+    if not getattr(cfg, "validation", False) or not validation_cache_ready(cfg):
+        return None
+    return LatentCacheDataLoader(validation_cache_dir(cfg), cfg.batch_size, device, seed=0, rank=rank, world=world,
+                                 require_mask=bool(getattr(cfg, "masked_training", False)), validation=True)
 
 
 def create_data_loader(config, model, device, rank: int = 0, world: int = 1):
     cfg = plain(config)
-    if not cache_ready(cfg):
+    need_train, need_validation = not cache_ready(cfg), validation_cache_needed(cfg)
+    if need_train or need_validation:
         if getattr(model, "vae_encoder", None) is None:
             raise RuntimeError("no latent cache at cache_dir and no VAE encoder on the model "
                                "(GenericTrainer.start attaches one when the cache must be built)")
-        build_cache(cfg, model, device, rank)
+        if need_train:
+            build_cache(cfg, model, device, rank)
+        if need_validation:
+            build_cache(cfg, model, device, rank, validation=True)
         if world > 1:
             torch.distributed.barrier()
         keep = ("text_encoder_1", "text_encoder_2") if getattr(model, "keep_text_encoders", False) else ()

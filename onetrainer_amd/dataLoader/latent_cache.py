@@ -6,6 +6,8 @@ Replaces what the reference's mgds pipeline does before and around the steps
   SampleVAEDistribution(mean) -> DiskCache -> AspectBatchSorting -> OutputPipelineModule.
 The mgds on-disk cache format is not pinned (mgds is not in this image); this build's format:
   <cache_dir>/index.json            {"version": 1, "samples": [{"file", "crop_resolution"}, ...]}
+                                    the held-out set's cache (<cache_dir>/validation) adds "concept_index" to every
+                                    entry and "concepts": [{"name", "path", "seed"}, ...] to the index
   <cache_dir>/<i:08d>.safetensors   latent_image [h, w, C] fp32 NHWC (VAE latent_dist.mean, unscaled; C = 4, FLUX.1 16),
                                     original_resolution / crop_offset / crop_resolution int64 [2],
                                     optional cached text states (text_encoder_*_hidden_state, pooled),
@@ -78,7 +80,7 @@ def scale_crop(img: torch.Tensor, scale_res, crop_res, offset):
 
 class LatentCacheWriter:
     def __init__(self, encode_fn, cache_dir: str, bucketing, device, encode_batch: int = 8, rank: int = 0,
-                 text_fn=None):
+                 text_fn=None, concepts=None):
         """encode_fn: [B, 3, H, W] fp32 [0, 1] on `device` -> latent NHWC fp32 [B, H/8, W/8, C]
         (module.vae.AutoencoderKLEncoder.encode).  text_fn (optional): {name: int64 token ids [B, T]}
         on `device` -> {cache key: [B, ...]} (module.text_encoder.encode_sdxl_text & co.), applied to
@@ -86,6 +88,7 @@ class LatentCacheWriter:
         self.encode_fn, self.cache_dir, self.bucketing = encode_fn, cache_dir, bucketing
         self.device, self.encode_batch, self.rank = torch.device(device), encode_batch, rank
         self.text_fn = text_fn
+        self.concepts = concepts   # the validation cache: {name, path, seed} of the concepts its samples index
 
     def write(self, samples):
         """samples: iterable of dicts {"image": PIL / tensor, optional "text": {name: tensor}, optional "mask":
@@ -100,7 +103,7 @@ class LatentCacheWriter:
             off = crop_offset(scale_res, crop_res)
             mask = _to_mask01(s["mask"]) if s.get("mask") is not None else None
             prepared.append((i, img, (h, w), scale_res, crop_res, off, dict(s.get("text") or {}), s.get("tokens"),
-                             mask))
+                             mask, s.get("concept_index")))
         by_res: dict = {}
         for p in prepared:
             by_res.setdefault(tuple(p[4]), []).append(p)
@@ -131,9 +134,12 @@ class LatentCacheWriter:
                     if self.rank == 0:
                         save_file(rec, os.path.join(self.cache_dir, fn))
                     index[i] = {"file": fn, "crop_resolution": list(p[4])}
+                    if p[9] is not None:
+                        index[i]["concept_index"] = int(p[9])
         if self.rank == 0:
             with open(os.path.join(self.cache_dir, INDEX), "w") as f:
-                json.dump({"version": 1, "samples": index}, f)
+                json.dump({"version": 1, "samples": index,
+                           **({} if self.concepts is None else {"concepts": self.concepts})}, f)
         return len(index)
 
 
@@ -142,11 +148,19 @@ class LatentCacheDataLoader:
     approximate_length(), get_data_loader() iterable of batches on `device`."""
 
     def __init__(self, cache_dir: str, batch_size: int, device, seed: int = 0, rank: int = 0, world: int = 1,
-                 text_defaults: dict | None = None, prefetch: bool = True, require_mask: bool = False):
+                 text_defaults: dict | None = None, prefetch: bool = True, require_mask: bool = False,
+                 validation: bool = False):
         """require_mask (masked training): batches carry latent_mask [B, 1, h, w]; a cached record without
-        one is an error.  Otherwise a cached mask is not emitted."""
+        one is an error.  Otherwise a cached mask is not emitted.
+        validation (the held-out set's cache): every pass emits every sample exactly once in a fixed order -- the
+        buckets in ascending resolution, cache index order within a bucket, no shuffle, nothing dropped, a short
+        last batch run short -- and each batch carries concept_index int32 [B] on the device (and
+        concept_index_host, the same on the host, for the accumulate launcher's range check)."""
         with open(os.path.join(cache_dir, INDEX)) as f:
-            self.index = json.load(f)["samples"]
+            meta = json.load(f)
+        self.index = meta["samples"]
+        self.validation = validation
+        self.concepts = meta.get("concepts", [])   # {name, path, seed} per concept index (validation caches)
         self.cache_dir, self.batch_size, self.device = cache_dir, batch_size, torch.device(device)
         self.seed, self.rank, self.world, self.epoch = seed, rank, world, -1
         self.text_defaults = text_defaults or {}
@@ -158,12 +172,24 @@ class LatentCacheDataLoader:
     def get_data_set(self):
         return self
 
+    def _validation_batches(self):
+        groups: dict = {}
+        for i, s in enumerate(self.index):
+            groups.setdefault(tuple(s["crop_resolution"]), []).append(i)
+        n = self.batch_size * self.world
+        return [idx[k:k + n] for r in sorted(groups) for idx in (groups[r],) for k in range(0, len(idx), n)]
+
     def start_next_epoch(self):
         self.epoch += 1
+        if self.validation:
+            self._batches = self._validation_batches()
+            return
         res = [tuple(s["crop_resolution"]) for s in self.index]
         self._batches = aspect_batches(res, self.batch_size * self.world, self.seed, self.epoch)
 
     def approximate_length(self):
+        if self.validation:
+            return len(self._validation_batches())
         if not self._batches:
             res = [tuple(s["crop_resolution"]) for s in self.index]
             return len(aspect_batches(res, self.batch_size * self.world, self.seed, 0))
@@ -188,6 +214,8 @@ class LatentCacheDataLoader:
                                  f"({self.cache_dir}) so it is rebuilt with them")
             out["latent_mask"] = torch.stack([r["latent_mask"] for r in recs])
         out["loss_weight"] = torch.ones(b)
+        if self.validation:
+            out["concept_index"] = torch.tensor([int(self.index[i]["concept_index"]) for i in idx], dtype=torch.int32)
         if torch.cuda.is_available():
             for k, v in list(out.items()):
                 if isinstance(v, torch.Tensor):
@@ -196,6 +224,8 @@ class LatentCacheDataLoader:
 
     def _to_device(self, host):
         dev = {}
+        if self.validation:   # before the upload: a pinned host copy stays behind for the launcher's range check
+            dev["concept_index_host"] = host["concept_index"]
         for k, v in host.items():
             if isinstance(v, tuple):
                 dev[k] = tuple(t.to(self.device, non_blocking=True) for t in v)
@@ -203,13 +233,18 @@ class LatentCacheDataLoader:
                 dev[k] = v.to(self.device, non_blocking=True)
         # the reference's [B, C, h, w] contract, as a view of the cached channels-last (NHWC) storage
         dev["latent_image"] = dev["latent_image"].permute(0, 3, 1, 2)
-        dev["concept_type"] = ["STANDARD"] * dev["latent_image"].shape[0]
+        dev["concept_type"] = ["VALIDATION" if self.validation else "STANDARD"] * dev["latent_image"].shape[0]
         return dev
 
     def get_data_loader(self):
         if not self._batches:
             self.start_next_epoch()
-        mine = [rank_slice(b, self.rank, self.world) for b in self._batches]
+        if self.validation:   # a short last batch: the first ranks take whole slices, the rest what is left (or none)
+            bs = self.batch_size
+            mine = [b[self.rank * bs:(self.rank + 1) * bs] for b in self._batches]
+            mine = [b for b in mine if b]
+        else:
+            mine = [rank_slice(b, self.rank, self.world) for b in self._batches]
         if not self.prefetch:
             for idx in mine:
                 yield self._to_device(self._load(idx))

@@ -1596,7 +1596,8 @@ def lora_dropout_consts(p: float) -> tuple:
     return int(math.floor(p * 4294967296.0)), (1.0 / (1.0 - p) if p < 1.0 else math.inf)
 
 
-def lora_dropout(t: torch.Tensor, seed_dev: torch.Tensor, site_id: int, row0: int, p: float) -> torch.Tensor:
+def lora_dropout(t: torch.Tensor, seed_dev: torch.Tensor, site_id: int, row0: int, p: float,
+                 rows_per: int = 0) -> torch.Tensor:
     """LoRA dropout in place on t = lora_down(x) (or u = dy (sB) in the backward): bf16, contiguous, [M, width] over
     its last dimension (LoRAModule.forward, modules/module/LoRAModule.py:319-323).  The mask is Philox4x32-10 stream 6
     at (site_id, row0 + m, column), keyed by the 64-bit seed in the one-element int64 device tensor seed_dev (read by
@@ -1612,6 +1613,11 @@ def lora_dropout(t: torch.Tensor, seed_dev: torch.Tensor, site_id: int, row0: in
     _req(0 <= site_id < (1 << 24), "lora_dropout: site_id outside [0, 2^24)")
     _req(row0 >= 0 and (row0 + M) * Wq <= (1 << 40), "lora_dropout: (row0 + M) * ceil(width / 4) above 2^40")
     thr, scale = lora_dropout_consts(p)
+    if rows_per:   # the validation pass: every sample's rows count from 0 (csrc/lora_dropout.hip)
+        _req(row0 == 0 and M % abs(rows_per) == 0, "lora_dropout: per-sample rows need row0 = 0 and whole samples")
+        check(lib().otamd_lora_dropout_per_sample(_p(t), M, width, _p(seed_dev), site_id, int(rows_per), thr, scale,
+                                                  stream_handle()), "otamd_lora_dropout_per_sample")
+        return t
     check(lib().otamd_lora_dropout(_p(t), M, width, _p(seed_dev), site_id, row0, thr, scale, stream_handle()),
           "otamd_lora_dropout")
     return t
@@ -1717,6 +1723,45 @@ def noise_ex(shape, seed, offset=0, offset_weight=0.0, perturbation_weight=0.0, 
                                out.numel() // max(1, int(shape[0])), float(offset_weight), float(perturbation_weight),
                                stream_handle()), "otamd_noise_ex")
     return out
+
+
+def noise_per_sample(shape, seed, offset_weight=0.0, perturbation_weight=0.0, dtype=BF16, device=None, out=None):
+    """NHWC noise [B, h, w, C] whose every sample is noise_ex((1, h, w, C), seed, offset=0): the deterministic noise
+    of the validation pass, independent of the batch and rank a sample is drawn in."""
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    _req(tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous() and len(shape) >= 2
+         and int(shape[0]) > 0, "noise_per_sample out")
+    check(lib().otamd_noise_per_sample(_p(out), int(dtype == F32), out.numel(), seed & 0xFFFFFFFFFFFFFFFF,
+                                       int(shape[-1]), out.numel() // int(shape[0]), float(offset_weight),
+                                       float(perturbation_weight), stream_handle()), "otamd_noise_per_sample")
+    return out
+
+
+def validation_accumulate(losses, concept_index, n_concepts, acc, index_host=None):
+    """acc[c] += (sum of losses[b], number of b) over the samples with concept_index[b] == c, in ascending b, in
+    double (csrc/validation.hip).  losses f32 [B] (a loss kernel's per-sample losses), concept_index int32 [B] on
+    the same device, acc f64 [n_concepts, 2] = (sum, count), updated in place.  index_host: the indices as a CPU
+    int32 tensor, when the caller has them: one outside [0, n_concepts) is then refused before the launch."""
+    hm = _host()
+    if hm is not None:
+        hm.validation_accumulate(losses, concept_index, int(n_concepts), acc, index_host, stream_handle())
+        return acc
+    _req(losses.is_cuda and losses.dtype == F32 and losses.dim() == 1 and losses.is_contiguous()
+         and 1 <= losses.numel() <= 1024, "validation_accumulate losses: contiguous f32 cuda [B], 1 <= B <= 1024")
+    B = losses.numel()
+    _req(concept_index.dtype == torch.int32 and concept_index.is_contiguous() and concept_index.numel() == B
+         and concept_index.device == losses.device,
+         "validation_accumulate concept_index: contiguous int32 [B] on the losses' device")
+    _req(n_concepts >= 1 and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == 2 * n_concepts
+         and acc.device == losses.device,
+         "validation_accumulate acc: contiguous f64 [n_concepts, 2] on the losses' device")
+    if index_host is not None:
+        _req(not index_host.is_cuda and index_host.dtype == torch.int32 and index_host.is_contiguous()
+             and index_host.numel() == B, "validation_accumulate index_host: contiguous CPU int32 [B]")
+    check(lib().otamd_validation_accumulate(_p(losses), _p(concept_index), _p(index_host), B, int(n_concepts), _p(acc),
+                                            stream_handle()), "otamd_validation_accumulate")
+    return acc
 
 
 def noise_stream(n, seed, stream_id, offset=0, dtype=F32, device=None):

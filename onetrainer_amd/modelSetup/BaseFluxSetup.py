@@ -20,8 +20,8 @@ import torch
 from .. import kernels as K
 from ..module import flux_ops as O
 from ..module import functional as Fn
-from .BaseStableDiffusionXLSetup import (draw_noise, draw_timesteps, loss_mask, loss_plan, nhwc_pair, plain_mse,
-                                         report_learning_rates)
+from .BaseStableDiffusionXLSetup import (draw_noise, draw_timesteps, loss_mask, loss_plan, nhwc_pair,
+                                         per_sample_losses, plain_mse, report_learning_rates, set_lora_rows)
 from ..util.config.plain import plain
 from ..util.timestep_table import TimestepTables
 
@@ -41,17 +41,19 @@ class BaseFluxSetup:
         """[B, 16, h, w] (reference contract; channels-last storage from this build's loaders) -> NHWC."""
         return lat.permute(0, 2, 3, 1).contiguous()
 
-    def _text(self, batch, config, rand, B):
-        """FluxModel.encode_text with cached outputs: per-encoder dropout masks from Random(seed)."""
+    def _text(self, batch, config, rand, B, per_sample=False):
+        """FluxModel.encode_text with cached outputs: per-encoder dropout masks from Random(seed); per_sample (the
+        validation pass): each mask is one draw repeated, what every sample gets as a batch of one."""
+        draws = (lambda: [rand.random()] * B) if per_sample else (lambda: [rand.random() for _ in range(B)])
         config = plain(config)
         pooled = batch["text_encoder_1_pooled_state"]
         ehs = batch["text_encoder_2_hidden_state"]
         p1, p2 = config.text_encoder.dropout_probability, config.text_encoder_2.dropout_probability
         if p1 is not None and p1 > 0:
-            m = torch.tensor([rand.random() > p1 for _ in range(B)], device=pooled.device).to(pooled.dtype)
+            m = torch.tensor([d > p1 for d in draws()], device=pooled.device).to(pooled.dtype)
             pooled = pooled * m[:, None]
         if p2 is not None and p2 > 0:
-            m = torch.tensor([rand.random() > p2 for _ in range(B)], device=ehs.device).to(ehs.dtype)
+            m = torch.tensor([d > p2 for d in draws()], device=ehs.device).to(ehs.dtype)
             ehs = ehs * m[:, None, None]
         return pooled.to(torch.bfloat16).contiguous(), ehs.to(torch.bfloat16).contiguous()
 
@@ -68,19 +70,22 @@ class BaseFluxSetup:
         mu = (w // 2) * (h // 2) * m + (0.5 - m * 256)
         return math.exp(mu)
 
-    def step_inputs(self, model, batch: dict, config, train_progress, *, deterministic: bool = False):
+    def step_inputs(self, model, batch: dict, config, train_progress, *, deterministic: bool = False,
+                    per_sample: bool = False):
         """(noise NHWC, timestep int32) of this micro-step (ModelSetupNoiseMixin._create_noise /
-        _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index."""
+        _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index.
+        per_sample (the validation pass, with deterministic): every sample gets the inputs of a batch of one on
+        rank 0 -- the noise counters and the LoRA dropout rows restart at 0 for each sample."""
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
-        lora = getattr(model, "transformer_lora", None)
-        if getattr(lora, "dropout_p", 0) > 0:   # LoRA dropout masks: the same seed as the noise
-            lora.set_dropout_seed(batch_seed)
         latent = batch["latent_image"]
         B, C, h, w = latent.shape
+        # LoRA dropout masks: the same seed as the noise
+        set_lora_rows(getattr(model, "transformer_lora", None), batch_seed, B if per_sample else 0)
         N = model.noise_scheduler.config["num_train_timesteps"]
         sample0 = self.dp_rank * B
-        noise = draw_noise(config, (B, h, w, C), batch_seed, sample0 * h * w * C, latent.dtype, latent.device)
+        noise = draw_noise(config, (B, h, w, C), batch_seed, sample0 * h * w * C, latent.dtype, latent.device,
+                           per_sample=per_sample)
         if deterministic:
             timestep = torch.full((B,), int(N * 0.5) - 1, dtype=torch.int32, device=latent.device)
         else:
@@ -88,18 +93,20 @@ class BaseFluxSetup:
                                       self._shift(config, h, w), latent.device)
         return noise, timestep
 
-    def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False) -> dict:
+    def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False,
+                per_sample: bool = False) -> dict:
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
         rand = Random(batch_seed)
         latent = self._nhwc_latent(batch["latent_image"])
         B, h, w, C = latent.shape
-        pooled, ehs = self._text(batch, config, rand, B)
+        pooled, ehs = self._text(batch, config, rand, B, per_sample)
         N = model.noise_scheduler.config["num_train_timesteps"]
-        if self.graph_inputs is not None:
+        if self.graph_inputs is not None and not per_sample:
             noise, timestep = self.graph_inputs
         else:
-            noise, timestep = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic)
+            noise, timestep = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic,
+                                               per_sample=per_sample)
         vc = model.vae.config
         model_in, target = K.flow_prologue(latent, noise, timestep, vc["scaling_factor"], vc["shift_factor"], N,
                                            cpad=C)
@@ -132,3 +139,8 @@ class BaseFluxSetup:
         return Fn.DiffusionLossFn.apply(pred, target, loss_mask(batch, plan, self.train_device), lw, data["timestep"],
                                         None, plan["loss_fn"], plan["gamma"], False, 1.0, strengths,
                                         plan["unmasked_weight"], plan["normalize"], scale, 1.0 / self.dp_world, N)
+
+    def validation_losses(self, model, batch: dict, data: dict, config) -> torch.Tensor:
+        """per-sample losses f32 [B] of predict()'s output, forward only (per_sample_losses)"""
+        return per_sample_losses(model, batch, data, loss_plan(plain(config), flow=True), 16, self.train_device, None,
+                                 False, model.noise_scheduler.config["num_train_timesteps"])

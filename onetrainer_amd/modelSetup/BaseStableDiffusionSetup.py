@@ -17,13 +17,15 @@ from ..util.config.plain import plain
 
 
 class BaseStableDiffusionSetup(BaseStableDiffusionXLSetup):
-    def _text(self, model, batch, config, rand, B):
+    def _text(self, model, batch, config, rand, B, per_sample=False):
         """StableDiffusionModel.encode_text with cached text (StableDiffusionModel.py:188-233):
-        pass-through, then the per-sample dropout mask drawn from Random(batch_seed)."""
+        pass-through, then the per-sample dropout mask drawn from Random(batch_seed); per_sample (the validation
+        pass): one draw repeated, what every sample gets as a batch of one."""
         config = plain(config)
         te = batch["text_encoder_hidden_state"]
         p = config.text_encoder.dropout_probability
         if p is not None and p > 0:
-            mask = torch.tensor([rand.random() > p for _ in range(B)], device=te.device).to(te.dtype)
+            keep = [rand.random() > p] * B if per_sample else [rand.random() > p for _ in range(B)]
+            mask = torch.tensor(keep, device=te.device).to(te.dtype)
             te = te * mask[:, None, None]
         return te.to(torch.bfloat16).contiguous(), None

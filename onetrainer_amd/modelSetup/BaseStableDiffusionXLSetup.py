@@ -101,14 +101,50 @@ def draw_timesteps(tables: TimestepTables, config, B, seed, sample0, N, shift, d
                        bias=config.noising_bias, weight=config.noising_weight, device=device, out=out, cdf=cdf)
 
 
-def draw_noise(config, shape, seed, offset, dtype, device, out=None):
+def draw_noise(config, shape, seed, offset, dtype, device, out=None, per_sample=False):
     """_create_noise (ModelSetupNoiseMixin.py:18-49) for an NHWC latent: Philox stream 1, plus the offset
-    (per sample and channel) and perturbation terms when their weights are > 0, in one kernel."""
+    (per sample and channel) and perturbation terms when their weights are > 0, in one kernel.
+    per_sample (the validation pass): every sample is the draw of a batch of one at offset 0, all terms included."""
     ow, pw = float(config.offset_noise_weight), float(config.perturbation_noise_weight)
+    if per_sample:
+        return K.noise_per_sample(shape, seed=seed, offset_weight=max(ow, 0.0), perturbation_weight=max(pw, 0.0),
+                                  dtype=dtype, device=device, out=out)
     if ow > 0 or pw > 0:
         return K.noise_ex(shape, seed=seed, offset=offset, offset_weight=max(ow, 0.0), perturbation_weight=max(pw, 0.0),
                           dtype=dtype, device=device, out=out)
     return K.noise(shape, seed=seed, offset=offset, dtype=dtype, device=device, out=out)
+
+
+def per_sample_losses(model, batch, data, plan, C, device, coeffs, v_pred, num_t=1000):
+    """the loss kernels' per-sample losses f32 [B] of a prediction, forward only (no autograd node, no host read):
+    element b is bit for bit what calculate_loss returns for sample b as a batch of one -- loss_weight, the timestep
+    weight, the strengths and the batch / accumulation scalers of `plan` included, the division by
+    gradient_accumulation_steps that train_step applies to the scalar not.  What the validation pass accumulates."""
+    lw = batch.get("loss_weight")
+    lw = lw.to(device, torch.float32).contiguous() if lw is not None else None
+    pred, target = nhwc_pair(data, C)
+    scale = float(plan["batch_size_scale"] * plan["ga_scale"])
+    if plain_mse(plan):
+        return K.mse_loss(pred, target, lw, mse_strength=plan["mse_strength"], scale=scale, loss_fn=plan["loss_fn"],
+                          gamma=plan["gamma"], v_pred=v_pred, ga=1.0, timestep=data["timestep"], coeffs=coeffs,
+                          num_t=num_t)[2]
+    return K.diffusion_loss(pred, target, loss_mask(batch, plan, device), lw, mse_strength=plan["mse_strength"],
+                            mae_strength=plan["mae_strength"], log_cosh_strength=plan["log_cosh_strength"],
+                            unmasked_weight=plan["unmasked_weight"], normalize=plan["normalize"], scale=scale,
+                            loss_fn=plan["loss_fn"], gamma=plan["gamma"], v_pred=v_pred, ga=1.0,
+                            timestep=data["timestep"], coeffs=coeffs, num_t=num_t)[2]
+
+
+def set_lora_rows(lora, batch_seed: int, per_sample_batch: int):
+    """LoRA dropout state of the step about to run: the masks' seed, and whether every sample's mask rows restart
+    at 0 (the validation pass; per_sample_batch = its batch size) or follow the global batch (training; 0).  Both
+    are written by every step_inputs call.  The row numbering is a host flag read when a launch is issued, and a
+    step being captured (trainer/step_graph.py) issues its launches without step_inputs: the validation pass
+    therefore puts the flag back to 0 itself when it ends (GenericTrainer.validate).  The seed is device memory,
+    read when a kernel runs, after the step_inputs that precedes every eager step and every replay."""
+    if getattr(lora, "dropout_p", 0) > 0:
+        lora.set_dropout_seed(batch_seed)
+        lora.per_sample_batch = per_sample_batch
 
 
 def report_learning_rates(model, lr_scheduler, tensorboard):
@@ -163,7 +199,9 @@ class BaseStableDiffusionXLSetup:
         tensor is a channels-last view (this build's loaders), one relayout copy otherwise (mgds)."""
         return lat.permute(0, 2, 3, 1).contiguous()
 
-    def _text(self, model, batch, config, rand, B):
+    def _text(self, model, batch, config, rand, B, per_sample=False):
+        """per_sample (the validation pass): every sample takes the draws of a batch of one, so each encoder's mask
+        is one draw of `rand` repeated"""
         config = plain(config)
         te1 = batch["text_encoder_1_hidden_state"]
         te2 = batch.get("text_encoder_2_hidden_state")
@@ -171,7 +209,8 @@ class BaseStableDiffusionXLSetup:
         for part, key in ((config.text_encoder, "te1"), (config.text_encoder_2, "te2")):
             p = part.dropout_probability
             if p is not None and p > 0:   # StableDiffusionXLModel.py:266-281 (host mask from Random(seed))
-                mask = torch.tensor([rand.random() > p for _ in range(B)], device=te1.device).to(te1.dtype)
+                keep = [rand.random() > p] * B if per_sample else [rand.random() > p for _ in range(B)]
+                mask = torch.tensor(keep, device=te1.device).to(te1.dtype)
                 if key == "te1":
                     te1 = te1 * mask[:, None, None]
                 else:
@@ -191,21 +230,23 @@ class BaseStableDiffusionXLSetup:
         parts = [config.text_encoder] + ([config.text_encoder_2] if hasattr(config, "text_encoder_2") else [])
         return all(not (p.dropout_probability or 0) > 0 for p in parts)
 
-    def step_inputs(self, model, batch: dict, config, train_progress, *, deterministic: bool = False, out=None):
+    def step_inputs(self, model, batch: dict, config, train_progress, *, deterministic: bool = False, out=None,
+                    per_sample: bool = False):
         """(noise, timestep) of this micro-step (ModelSetupNoiseMixin._create_noise /
-        _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index."""
+        _get_timestep_discrete): Philox seeded by `batch_seed`, counter = GLOBAL batch index.
+        per_sample (the validation pass, with deterministic): every sample gets the inputs of a batch of one on
+        rank 0 -- the noise counters and the LoRA dropout rows restart at 0 for each sample."""
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
-        lora = getattr(model, "unet_lora", None)
-        if getattr(lora, "dropout_p", 0) > 0:   # LoRA dropout masks: the same seed, written outside a captured step
-            lora.set_dropout_seed(batch_seed)
+        # LoRA dropout masks: the same seed, written outside a captured step
+        set_lora_rows(getattr(model, "unet_lora", None), batch_seed, batch["latent_image"].shape[0] if per_sample else 0)
         lat = batch["latent_image"]
         B = lat.shape[0]
         shape = tuple(self._nhwc_latent(lat).shape) if out is None else tuple(out[0].shape)
         _, h, w, C = shape
         sample0 = self.dp_rank * B                       # global-batch index of this rank's first sample
         noise = draw_noise(config, shape, batch_seed, sample0 * h * w * C, lat.dtype, lat.device,
-                           None if out is None else out[0])
+                           None if out is None else out[0], per_sample=per_sample)
         N = model.noise_scheduler.config["num_train_timesteps"]
         if deterministic:
             timestep = torch.full((B,), int(N * 0.5) - 1, dtype=torch.int32, device=lat.device)
@@ -216,18 +257,20 @@ class BaseStableDiffusionXLSetup:
                                       lat.device, out=None if out is None else out[1])
         return noise, timestep
 
-    def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False) -> dict:
+    def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False,
+                per_sample: bool = False) -> dict:
         config = plain(config)
         batch_seed = 0 if deterministic else train_progress.global_step
         rand = Random(batch_seed)
         latent = self._nhwc_latent(batch["latent_image"])
         B, h, w, C = latent.shape
         sf = model.vae.config["scaling_factor"]
-        ehs, pooled = self._text(model, batch, config, rand, B)
-        if self.graph_inputs is not None:
+        ehs, pooled = self._text(model, batch, config, rand, B, per_sample)
+        if self.graph_inputs is not None and not per_sample:
             noise, timestep = self.graph_inputs
         else:
-            noise, timestep = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic)
+            noise, timestep = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic,
+                                               per_sample=per_sample)
         ptype = model.noise_scheduler.config["prediction_type"]
         unet_in, target, _ = K.ddpm_prologue(latent, noise, timestep, model.noise_scheduler.coeffs, sf,
                                              1 if ptype == "v_prediction" else 0)
@@ -260,3 +303,8 @@ class BaseStableDiffusionXLSetup:
                                         model.noise_scheduler.coeffs, plan["loss_fn"], plan["gamma"], v_pred, 1.0,
                                         strengths, plan["unmasked_weight"], plan["normalize"], scale,
                                         1.0 / self.dp_world)
+
+    def validation_losses(self, model, batch: dict, data: dict, config) -> torch.Tensor:
+        """per-sample losses f32 [B] of predict()'s output, forward only (per_sample_losses)"""
+        return per_sample_losses(model, batch, data, loss_plan(plain(config)), 4, self.train_device,
+                                 model.noise_scheduler.coeffs, data.get("prediction_type") == "v_prediction")

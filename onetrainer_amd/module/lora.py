@@ -167,6 +167,10 @@ class LoRAWrapper:
         self.site_of = {}
         self.dropout_p = 0.0   # LoRAModuleWrapper.set_dropout
         self.dp_rank = 0       # data-parallel rank: rank r draws rows [r M, (r + 1) M) of the global mask
+        # the validation pass (the setups' step_inputs(per_sample=True)): the batch size while every sample's mask
+        # rows restart at 0, else 0; token_major: rows are r = t * B + b (the FLUX transformer), not sample-major
+        self.per_sample_batch = 0
+        self.token_major = prefix == "lora_transformer"
         # the dropout seed (batch_seed of the step), read by the kernel from device memory so that a replayed step
         # graph draws a new mask; written eagerly before every step (the setups' step_inputs)
         self.drop_seed = torch.zeros(1, dtype=torch.int64, device=model.device)
@@ -263,6 +267,10 @@ class LoRAWrapper:
         """mask t = down(x) (forward) or u = dy (sB) (backward) of `site` in place: t is [M, P r] over its last
         dimension, its rows sample-major, row 0 being row dp_rank * M of the global batch's tensor"""
         M = t.numel() // t.shape[-1]
+        B = self.per_sample_batch
+        if B:   # the validation pass: each sample's rows count from its own row 0, on every rank
+            return K.lora_dropout(t, self.drop_seed, site.site_id, 0, self.dropout_p,
+                                  rows_per=-B if self.token_major else M // B)
         return K.lora_dropout(t, self.drop_seed, site.site_id, self.dp_rank * M, self.dropout_p)
 
     # ----- parameters ----------------------------------------------------------------------------

@@ -57,6 +57,7 @@ class GenericTrainer(TimedActionMixin):
         self.sample_configs: list = []     # the run's sample definitions (util/config/SampleConfig.py)
         self.sample_prompt_states = None   # ready text states for every sample (callers without tokenizers, tests)
         self.sample_paths: list[str] = []  # files written so far (rank 0)
+        self.validation_data_loader = None   # the held-out set (dataLoader/create.create_validation_data_loader)
         self._ctl_group = None
         self.agreements = 0
         self.rank, self.world = 0, 1
@@ -69,16 +70,19 @@ class GenericTrainer(TimedActionMixin):
             else torch.device(str(cfg.train_device))
         if self.model is None:
             self.model = create.create_model(cfg, self.device, seed=self.seed)
-        from ..dataLoader.create import attach_cache_encoders, cache_ready, create_data_loader, has_concepts
+        from ..dataLoader.create import (attach_cache_encoders, cache_ready, create_data_loader,
+                                         create_validation_data_loader, has_concepts, validation_cache_needed)
         # create.create_data_loader (create.py:391-431) when there is data to load: a latent cache at
         # cache_dir or concepts to cache; step-level callers (bench, tests) pass batches to train_step
         want_data = self.data_loader is None and (cache_ready(cfg) or has_concepts(cfg))
-        if want_data and not cache_ready(cfg):   # the model loader fills the caching encoders
+        if want_data and (not cache_ready(cfg) or validation_cache_needed(cfg)):   # the model loader fills the caching encoders
             attach_cache_encoders(self.model, cfg, self.device)
         self._setup_sampling()                   # ... and the VAE decoder, only when samples are configured
         self._load_weights()
         if want_data:
             self.data_loader = create_data_loader(cfg, self.model, self.device, self.rank, self.world)
+        if self.validation_data_loader is None:   # None again when validation is off or nothing is held out
+            self.validation_data_loader = create_validation_data_loader(cfg, self.device, self.rank, self.world)
         if self.model_setup is None:
             self.model_setup = create.create_model_setup(cfg, self.device, self.rank, self.world)
         self.model_setup.setup_model(self.model, cfg)
@@ -265,6 +269,79 @@ class GenericTrainer(TimedActionMixin):
             self._after_eval()
         self.sample_paths += written
         return written
+
+    # ----- validation loss ---------------------------------------------------------------------
+    def _needs_validate(self, tp) -> bool:
+        """GenericTrainer.py:521-524 behind `if self.config.validation` (:751)"""
+        cfg = self.config
+        return bool(cfg.validation) and self.repeating_action_needed("validate", cfg.validate_after,
+                                                                     cfg.validate_after_unit, tp)
+
+    def validate(self, train_progress: TrainProgress | None = None, global_step: int | None = None,
+                 collect: bool = False) -> dict | None:
+        """__validate (GenericTrainer.py:319-389): the loss of every held-out sample with the deterministic inputs
+        (seed 0, the middle timestep), averaged per validation concept into `loss/validation_step/<label>` and
+        `loss/validation_step/total_average`, at `global_step` (default: the progress's).
+
+        The reference runs batch size 1 and reads loss.item() per image.  Here the set runs at the training batch
+        size in its aspect buckets, every sample with the inputs it would have as a batch of one
+        (predict(per_sample=True)); the per-sample losses go into per-concept (sum, count) pairs on the device
+        (csrc/validation.hip) and the host reads them once, after the last batch (one all-gather under data parallel).
+        The weights are the trained ones as the store holds them: not the EMA, and for a schedule-free optimizer the
+        gradient point y, as in the reference, which validates without __before_eval.
+
+        Training is left alone: the pass runs under no_grad, outside any captured step graph, with the weight-gradient
+        stream joined before and after; it writes no parameter, gradient or optimizer state.  Of what step_inputs
+        writes, the LoRA dropout's per-sample row numbering is a host flag that a step being captured would read
+        without step_inputs having run, so it is put back when the pass ends; the dropout seed lives in device
+        memory and is written again by the next training step's step_inputs before any kernel, replayed or eager,
+        reads it.  A captured step's input buffers are not touched (the pass draws into tensors of its own).  Returns {"acc": host f64 [n, 2], "scalars": [(tag, value)], "sample_losses":
+        (concept indices, losses) in loader order when `collect`}, or None when there is nothing held out."""
+        from .. import kernels as K
+        from ..module import streams as S
+        from .validation import gather_ranks, validation_scalars
+        cfg, model, setup = self.config, self.model, self.model_setup
+        tp = train_progress or model.train_progress
+        loader = self.validation_data_loader
+        if loader is None:
+            return None
+        data = loader.get_data_set()
+        data.start_next_epoch()
+        if data.approximate_length() == 0 or not loader.concepts:
+            return None
+        step = tp.global_step if global_step is None else global_step
+        concepts = loader.concepts
+        acc = torch.zeros((len(concepts), 2), dtype=torch.float64, device=self.device)
+        kept = []
+        S.join()
+        try:
+            with torch.no_grad():
+                for batch in loader.get_data_loader():   # no host read inside this loop
+                    out = setup.predict(model, batch, cfg, tp, deterministic=True, per_sample=True)
+                    losses = setup.validation_losses(model, batch, out, cfg)
+                    K.validation_accumulate(losses, batch["concept_index"], len(concepts), acc,
+                                            batch.get("concept_index_host"))
+                    if collect:
+                        kept.append((batch["concept_index_host"], losses))
+        finally:
+            # the per-sample row numbering must not outlive the pass: a step captured right after it
+            # (trainer/step_graph.py) runs predict without step_inputs and would record the validation form of the
+            # LoRA dropout launch into its graph
+            for name in ("unet_lora", "transformer_lora"):
+                lora = getattr(model, name, None)
+                if getattr(lora, "per_sample_batch", 0):
+                    lora.per_sample_batch = 0
+            S.join()
+        host = gather_ranks(acc, self.world).cpu()   # the pass's one device-to-host read
+        scalars = validation_scalars(host, concepts)
+        if self.tensorboard is not None:
+            for tag, v in scalars:
+                self.tensorboard.add_scalar(tag, v, step)
+        result = {"acc": host, "scalars": scalars, "sample_losses": None}
+        if collect:
+            result["sample_losses"] = (torch.cat([i for i, _ in kept]).tolist() if kept else [],
+                                       torch.cat([l for _, l in kept]).cpu() if kept else torch.zeros(0))
+        return result
 
     def _attach_norm_overlap(self):
         """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor, CAME, Prodigy): clip_grad_norm_'s norm pass runs during backward
@@ -528,6 +605,10 @@ class GenericTrainer(TimedActionMixin):
                                      for u in (cfg.backup_after_unit, cfg.save_every_unit)
                                      + ((cfg.sample_after_unit,) if any(s.enabled for s in self.sample_configs)
                                         else ()))
+        if self.world > 1 and cfg.validation and TimedActionMixin._unit(cfg.validate_after_unit) in self.WALLCLOCK:
+            # a wall-clock timer fires on one rank and not another, and the pass ends in a collective
+            raise NotImplementedError("validate_after_unit SECOND / MINUTE / HOUR under data parallel is not built: "
+                                      "use STEP or EPOCH")
         steps = 0
         # losses are read from the device every `flush_every` steps: printed when log_every is set, written as
         # the loss scalars either way (the reference logs them every update step, GenericTrainer.py:723-733)
@@ -550,7 +631,12 @@ class GenericTrainer(TimedActionMixin):
                     if not self._has_gradient:
                         self._run_commands(tp, self._agreement_point(tp))
                     gs, update = tp.global_step, self._is_update_step(tp)
+                    # GenericTrainer.py:751-752: the timer is asked with this step's progress, the pass runs after
+                    # the step (and its optimizer update) and before the next one
+                    validate = self._needs_validate(tp)
                     loss = self.train_step(batch)
+                    if validate:
+                        self.validate(tp, global_step=gs)
                     self.loss_history.append(loss)
                     self._micro_losses.append(loss)
                     if update:   # GenericTrainer.py:723-733 (values resolved at the next flush point)

@@ -163,6 +163,10 @@ class TrainConfig:
     sample_image_format: str = "JPG"
     samples_to_tensorboard: bool = True
     non_ema_sampling: bool = True
+    # validation loss on the concepts of type VALIDATION (TrainConfig.py:774-776; trainer.GenericTrainer.validate)
+    validation: bool = False
+    validate_after: float = 1
+    validate_after_unit: str = "EPOCH"
     text_encoder_layer_skip: int = 0          # TrainConfig.py:873,883
     text_encoder_2_layer_skip: int = 0
     # concepts (TrainConfig.py:793-794): inline list of ConceptConfig dicts, else the concept file
