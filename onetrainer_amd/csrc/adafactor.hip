@@ -27,8 +27,9 @@
 // Arithmetic: fp32 element ops in the reference's order (-ffp-contract=off; the fused multiply-adds are the
 // ones torch's CPU add_(alpha=) kernels use), fp32 sums.  tests/_oracle_adafactor.py restates it.
 //
-// The unorm kernel, the slab walk, the parameter write and the EMA are shared with came.hip and live in
-// adafactor_walk.h.  The statistics kernel is not: came_stats_kernel (came.hip) restates its three-mode body.
+// The unorm kernel, the slab walk and the EMA are shared with came.hip and live in adafactor_walk.h; the masked loads
+// and stores, the clip rounding and the parameter write are every flat-store optimizer's (flat_store.h).  The
+// statistics kernel is not shared: came_stats_kernel (came.hip) restates its three-mode body.
 #include "adafactor_walk.h"
 
 struct AdafactorGroup {
@@ -40,7 +41,7 @@ struct AdafactorGroup {
   int scale_parameter;
   int pad;
 };
-struct AdafactorGroups { AdafactorGroup g[AF_MAX_GROUPS]; };
+struct AdafactorGroups { AdafactorGroup g[FS_MAX_GROUPS]; };
 
 // ---- 1: statistics --------------------------------------------------------------------------------------------
 template <typename TP, typename TG, bool BFROUND>
@@ -66,12 +67,12 @@ __global__ void __launch_bounds__(AF_THREADS) af_stats_kernel(const TP* __restri
 
   if (T.mode == 0) {
     for (long long i = sl.row0 + tid; i < sl.row1; i += AF_THREADS) {
-      const float g = af_clip<BFROUND>(af_load1<TG>(Gr, T.offset + i), coef, clip);
+      const float g = fs_clip<BFROUND>(fs_load1<TG>(Gr, T.offset + i), coef, clip);
       const float upd = g * g + G.eps1;
       float* v = state + T.full_off + i;
       *v = af_ema(*v, upd, G.beta2t, G.one_minus_beta2t);
       if (scale) {
-        const float p = af_load1<TP>(P, T.offset + i);
+        const float p = fs_load1<TP>(P, T.offset + i);
         pacc += (double)(p * p);
       }
     }
@@ -86,12 +87,12 @@ __global__ void __launch_bounds__(AF_THREADS) af_stats_kernel(const TP* __restri
       __syncthreads();   // the previous stage's readers are done
       for (long long v = a0 + 8 * tid; v < e1; v += 8 * AF_THREADS) {
         float f[8];
-        af_load8<TG>(Gr, v, f);
+        fs_load8<TG>(Gr, v, f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) s_stage[v - a0 + j] = af_clip<BFROUND>(f[j], coef, clip);
+        for (int j = 0; j < 8; ++j) s_stage[v - a0 + j] = fs_clip<BFROUND>(f[j], coef, clip);
         if (scale) {
           float q[8];
-          af_load8<TP>(P, v, q);
+          fs_load8<TP>(P, v, q);
           float s = 0.f;
 #pragma unroll
           for (int j = 0; j < 8; ++j)
@@ -145,12 +146,12 @@ __global__ void __launch_bounds__(AF_THREADS) af_stats_kernel(const TP* __restri
         const long long v = (e0 & ~7LL) + 8 * j;
         if (v < e1) {
           float f[8];
-          af_load8<TG>(Gr, v, f);
+          fs_load8<TG>(Gr, v, f);
 #pragma unroll
-          for (int jj = 0; jj < 8; ++jj) s_stage[i * W8 + 8 * j + jj] = af_clip<BFROUND>(f[jj], coef, clip);
+          for (int jj = 0; jj < 8; ++jj) s_stage[i * W8 + 8 * j + jj] = fs_clip<BFROUND>(f[jj], coef, clip);
           if (scale) {
             float p8[8];
-            af_load8<TP>(P, v, p8);
+            fs_load8<TP>(P, v, p8);
             float s = 0.f;
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj)
@@ -259,7 +260,7 @@ __global__ void __launch_bounds__(AF_THREADS) af_apply_kernel(TP* __restrict__ P
   const AdafactorGroup G = groups.g[T.group];
   const bool clip = clip_coef != nullptr;
   const float coef = clip ? clip_coef[0] : 1.f;
-  const uint32_t k = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t k = fs_seed_key(seed);
   // update.div_((rms(update) / clip_threshold).clamp_(min=1.0)); lr = lr * max(eps2, RMS) (scale_parameter)
   const float denom = fmaxf(scal[4 * sl.tensor + 1] / G.clip_threshold, 1.f);
   const bool scale = G.scale_parameter != 0;
@@ -269,7 +270,7 @@ __global__ void __launch_bounds__(AF_THREADS) af_apply_kernel(TP* __restrict__ P
   af_walk<TG, FORM == 0>(Gr, state, scratch, T, sl, coef, clip, s_r, s_c,
                          [&](long long v, const float* g, const float* fac, unsigned valid) {
                            float p[8];
-                           af_load8<TP>(P, v, p);
+                           fs_load8<TP>(P, v, p);
 #pragma unroll
                            for (int j = 0; j < 8; ++j) {
                              float u = fac[j] * g[j];
@@ -279,7 +280,7 @@ __global__ void __launch_bounds__(AF_THREADS) af_apply_kernel(TP* __restrict__ P
                              if (decay) x = fmaf(x, alpha, x);   // p.add_(p, alpha=-weight_decay * lr)
                              p[j] = x - u;                       // p.add_(-update)
                            }
-                           af_write_params<FORM>(P, W, v, p, valid, sr, k);
+                           fs_write_params<FORM>(P, W, v, p, valid, sr, k);
                          });
 }
 
@@ -320,22 +321,15 @@ OTAMD_API int otamd_adafactor_step(void* p, const void* g, void* w16, int form, 
                                    const void* slabs, int s_begin, int s_end, const AdafactorGroup* groups,
                                    int n_groups, const float* clip_coef, int stochastic_rounding,
                                    unsigned long long seed, hipStream_t stream) {
-  if (!p || !g || !state || !scratch || !slab_sq || !scal || !tensors || !slabs || !groups || form < 0 || form > 2 ||
-      (form == 2 && !w16) || n_groups < 1 || n_groups > AF_MAX_GROUPS || t_begin < 0 || t_end < t_begin ||
-      s_begin < 0 || s_end < s_begin)
+  if (!p || !g || !state || !scratch || !slab_sq || !scal || !tensors || !slabs || !groups || !fs_form_ok(form, w16) ||
+      !fs_group_count_ok(n_groups) || t_begin < 0 || t_end < t_begin || s_begin < 0 || s_end < s_begin)
     return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)w16 | (uintptr_t)state | (uintptr_t)scratch) & 15) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, g, w16, state, scratch)) return OTAMD_EINVAL;
   if (t_end == t_begin || s_end == s_begin) return OTAMD_OK;
-  AdafactorGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  const AdafactorTensor* T = (const AdafactorTensor*)tensors;
-  const AdafactorSlab* S = (const AdafactorSlab*)slabs;
-  if (form == 0)
-    return af_launch<bf16_t, bf16_t, 0>(p, g, nullptr, state, scratch, slab_sq, scal, T, t_begin, t_end, S, s_begin, s_end,
-                                        G, clip_coef, stochastic_rounding, seed, stream);
-  if (form == 1)
-    return af_launch<float, float, 1>(p, g, nullptr, state, scratch, slab_sq, scal, T, t_begin, t_end, S, s_begin, s_end, G,
-                                      clip_coef, 0, seed, stream);
-  return af_launch<float, bf16_t, 2>(p, g, w16, state, scratch, slab_sq, scal, T, t_begin, t_end, S, s_begin, s_end, G,
-                                     clip_coef, 0, seed, stream);
+  const AdafactorGroups G = fs_groups_arg<AdafactorGroups>(groups, n_groups);
+  return fs_dispatch(form, [&](auto F) {
+    return af_launch<typename decltype(F)::TP, typename decltype(F)::TG, F.form>(
+        p, g, F.w(w16), state, scratch, slab_sq, scal, (const AdafactorTensor*)tensors, t_begin, t_end,
+        (const AdafactorSlab*)slabs, s_begin, s_end, G, clip_coef, F.sr(stochastic_rounding), seed, stream);
+  });
 }

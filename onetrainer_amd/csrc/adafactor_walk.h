@@ -1,13 +1,13 @@
-// What the factored optimizers (adafactor.hip, came.hip) share: the tensor and slab tables, the masked 16-byte
-// loads and stores, the pending-clip rounding, the EMA, the fixed-order block sum, and, each written once here:
+// What the factored optimizers (adafactor.hip, came.hip) share beyond flat_store.h: the tensor and slab tables, the
+// EMA, torch's rsqrt, the fixed-order block sum, and, each written once here:
 //   af_walk          every 8-aligned vector of a slab with its rsqrt factors (af_unorm_kernel and the apply kernels)
 //   af_unorm_kernel  sum u^2 per slab, one template that each file instantiates under its own tag
-//   af_write_params  the parameter write of the apply kernels: bf16 rounding and the masked store of the three forms
-// The statistics kernels stay in the two .hip files.  adafactor.hip's header comment describes the layout and the modes.
+// The masked 16-byte loads and stores, the pending-clip rounding and the parameter write of the apply kernels
+// (fs_write_params) are flat_store.h's.  The statistics kernels stay in the two .hip files.  adafactor.hip's header
+// comment describes the layout and the modes.
 #pragma once
-#include "common.h"
+#include "flat_store.h"
 
-#define AF_MAX_GROUPS 8
 #define AF_STAGE 4096   // floats of one LDS stage
 #define AF_CT 4080      // widest column tile: its padded row (width + up to 15 floats of alignment) fits a stage
 #define AF_THREADS 256
@@ -32,27 +32,6 @@ struct AdafactorSlab {
   int pad;
 };
 
-// eight elements at an 8-aligned element index
-template <typename T> __device__ __forceinline__ void af_load8(const T* base, long long e, float* f);
-template <> __device__ __forceinline__ void af_load8<bf16_t>(const bf16_t* base, long long e, float* f) {
-  const bf8 v = *reinterpret_cast<const bf8*>(base + e);
-  unpack8(v, f);
-}
-template <> __device__ __forceinline__ void af_load8<float>(const float* base, long long e, float* f) {
-  const float4 a = *reinterpret_cast<const float4*>(base + e);
-  const float4 b = *reinterpret_cast<const float4*>(base + e + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename T> __device__ __forceinline__ float af_load1(const T* base, long long e);
-template <> __device__ __forceinline__ float af_load1<bf16_t>(const bf16_t* base, long long e) { return bf2f(base[e]); }
-template <> __device__ __forceinline__ float af_load1<float>(const float* base, long long e) { return base[e]; }
-
-// the pending global-norm clip on one gradient element, rounded as the AdamW kernels round it
-template <bool BFROUND> __device__ __forceinline__ float af_clip(float g, float coef, bool clip) {
-  if (!clip) return g;
-  return BFROUND ? rbf(g * coef) : g * coef;
-}
-
 __device__ __forceinline__ float af_rsqrt(float x) { return 1.f / sqrtf(x); }   // torch's CPU rsqrt
 
 // block sum of one double in a fixed order; red: 4 doubles
@@ -69,43 +48,6 @@ __device__ __forceinline__ float af_ema(float state, float mean, float beta, flo
   return fmaf(mean, omb, state * beta);
 }
 
-// eight values at an 8-aligned element index; partial vectors element-wise (neighbouring slabs never write the
-// same bytes)
-__device__ __forceinline__ void af_store8(float* base, long long v, const float* x, unsigned valid) {
-  if (valid == 0xFFu) {
-    *reinterpret_cast<float4*>(base + v) = make_float4(x[0], x[1], x[2], x[3]);
-    *reinterpret_cast<float4*>(base + v + 4) = make_float4(x[4], x[5], x[6], x[7]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (valid >> j & 1) base[v + j] = x[j];
-  }
-}
-__device__ __forceinline__ void af_store8(bf16_t* base, long long v, const float* x, unsigned valid) {
-  if (valid == 0xFFu) {
-    *reinterpret_cast<bf8*>(base + v) = pack8(x);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (valid >> j & 1) base[v + j] = f2bf(x[j]);
-  }
-}
-
-// ---- the parameter write of an apply kernel -----------------------------------------------------------------------
-// FORM 0: bf16 store, x rounded here (stochastic bits of key k at the store index, or RNE); 1: fp32 store; 2: fp32
-// master + bf16 working copy W = rne(master)
-template <int FORM, typename TP>
-__device__ __forceinline__ void af_write_params(TP* P, bf16_t* W, long long v, float* x, unsigned valid, int sr,
-                                                uint32_t k) {
-  if constexpr (FORM == 0) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      x[j] = sr ? __uint_as_float((__float_as_uint(x[j]) + sr_bits(k, (uint64_t)(v + j))) & 0xFFFF0000u) : rbf(x[j]);
-  }
-  af_store8(P, v, x, valid);
-  if constexpr (FORM == 2) af_store8(W, v, x, valid);
-}
-
 // ---- the walk: every 8-aligned vector of a slab with its gradient and factors -----------------------------------
 // body(v, g, fac, valid): v = store element index of the vector, g = clipped gradients, fac = rsqrt factors,
 // valid = lane mask of the elements that belong to the slab
@@ -119,12 +61,12 @@ __device__ __forceinline__ void af_walk(const TG* __restrict__ Gr, const float* 
     const long long e0 = T.offset + sl.row0, e1 = T.offset + sl.row1;
     for (long long v = (e0 & ~7LL) + 8 * tid; v < e1; v += 8 * AF_THREADS) {
       float g[8], fac[8];
-      af_load8<TG>(Gr, v, g);
+      fs_load8<TG>(Gr, v, g);
       unsigned valid = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool ok = v + j >= e0 && v + j < e1;
-        g[j] = af_clip<BFROUND>(g[j], coef, clip);
+        g[j] = fs_clip<BFROUND>(g[j], coef, clip);
         fac[j] = ok ? af_rsqrt(state[T.full_off + (v + j - T.offset)]) : 0.f;
         valid |= ok ? 1u << j : 0u;
       }
@@ -143,7 +85,7 @@ __device__ __forceinline__ void af_walk(const TG* __restrict__ Gr, const float* 
       __syncthreads();
       for (long long v = (e0 & ~7LL) + 8 * tid; v < e1; v += 8 * AF_THREADS) {
         float g[8], fac[8];
-        af_load8<TG>(Gr, v, g);
+        fs_load8<TG>(Gr, v, g);
         const int j0 = v < e0 ? (int)(e0 - v) : 0;
         const int li = (int)(v + j0 - e0);
         int ml = li / rc;
@@ -153,7 +95,7 @@ __device__ __forceinline__ void af_walk(const TG* __restrict__ Gr, const float* 
         unsigned valid = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          g[j] = af_clip<BFROUND>(g[j], coef, clip);
+          g[j] = fs_clip<BFROUND>(g[j], coef, clip);
           fac[j] = 0.f;
           if (j >= j0 && v + j < e1) {
             fac[j] = s_r[ml * T.rows + r] * s_c[ml * T.cols + c];
@@ -182,13 +124,13 @@ __device__ __forceinline__ void af_walk(const TG* __restrict__ Gr, const float* 
       const long long v = (e0 & ~7LL) + 8 * j;
       if (v >= e1) continue;
       float g[8], fac[8];
-      af_load8<TG>(Gr, v, g);
+      fs_load8<TG>(Gr, v, g);
       unsigned valid = 0;
       const float rf = s_r[i];
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) {
         const bool ok = v + jj >= e0 && v + jj < e1;
-        g[jj] = af_clip<BFROUND>(g[jj], coef, clip);
+        g[jj] = fs_clip<BFROUND>(g[jj], coef, clip);
         fac[jj] = ok ? rf * s_c[v + jj - e0] : 0.f;
         valid |= ok ? 1u << jj : 0u;
       }

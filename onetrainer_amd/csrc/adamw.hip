@@ -13,12 +13,8 @@
 // contraction is introduced.
 //
 // HBM traffic per bf16 element: read p,g,m,v (8 B) + write p,m,v (6 B) = 14 B.
-#include "common.h"
-
-#include <algorithm>
-#include <cstdlib>
-
-#define ADAMW_MAX_GROUPS 8
+// The group look-up, the chunk table, the seed fold and the host checks are flat_store.h's.
+#include "flat_store.h"
 
 struct AdamwGroup {
   long long begin, end;     // element range [begin, end) of this group in the flat store
@@ -32,7 +28,7 @@ struct AdamwGroup {
   float pad;
 };
 struct AdamwGroups {
-  AdamwGroup g[ADAMW_MAX_GROUPS];
+  AdamwGroup g[FS_MAX_GROUPS];
   int n;
 };
 
@@ -79,14 +75,6 @@ __device__ __forceinline__ void adamw_elem_bf16(float& p, float g, float& m, flo
   }
 }
 
-__device__ __forceinline__ int find_group(const AdamwGroups& G, long long e) {
-  int gi = 0;
-#pragma unroll
-  for (int i = 1; i < ADAMW_MAX_GROUPS; ++i)
-    if (i < G.n && e >= G.g[i].begin) gi = i;
-  return gi;
-}
-
 // flat bf16 store; n multiple of 8 (the store pads every tensor to 8 elements)
 __global__ void __launch_bounds__(256) adamw_bf16_kernel(bf16_t* __restrict__ P, const bf16_t* __restrict__ Gr,
                                                          bf16_t* __restrict__ M, bf16_t* __restrict__ V, long long v0,
@@ -95,7 +83,7 @@ __global__ void __launch_bounds__(256) adamw_bf16_kernel(bf16_t* __restrict__ P,
                                                          unsigned long long seed) {
   const bool clip = clip_coef != nullptr;
   const float coef = clip ? clip_coef[0] : 1.f;
-  const uint32_t k = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t k = fs_seed_key(seed);
   const long long stride = (long long)gridDim.x * blockDim.x;
   long long i = v0 + blockIdx.x * (long long)blockDim.x + threadIdx.x;
   // software pipeline: the next granule's four loads are in flight while this one is computed
@@ -112,7 +100,7 @@ __global__ void __launch_bounds__(256) adamw_bf16_kernel(bf16_t* __restrict__ P,
       mn = reinterpret_cast<const bf8*>(M)[in]; vn = reinterpret_cast<const bf8*>(V)[in];
     }
     const long long e0 = i * 8;
-    const int gi = find_group(groups, e0);
+    const int gi = fs_find_group(groups, e0);
     const AdamwGroup& G = groups.g[gi];
     if (e0 < G.end) {  // else: padding tail beyond the last group
       float p[8], g[8], m[8], v[8];
@@ -164,7 +152,7 @@ __global__ void __launch_bounds__(1024) adamw_bf16_lut_kernel(bf16_t* __restrict
   __syncthreads();
   const bool clip = clip_coef != nullptr;
   const float coef = clip ? clip_coef[0] : 1.f;
-  const uint32_t k = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t k = fs_seed_key(seed);
   const long long stride = (long long)gridDim.x * blockDim.x;
   long long i = v0 + blockIdx.x * (long long)blockDim.x + threadIdx.x;
   bf8 pv, gv, mv, vv;
@@ -180,7 +168,7 @@ __global__ void __launch_bounds__(1024) adamw_bf16_lut_kernel(bf16_t* __restrict
       mn = ldv<NT>(M, in); vn = ldv<NT>(V, in);
     }
     const long long e0 = i * 8;
-    const int gi = find_group(groups, e0);
+    const int gi = fs_find_group(groups, e0);
     const AdamwGroup& G = groups.g[gi];
     if (e0 < G.end) {
       float p[8], g[8], m[8], v[8];
@@ -218,7 +206,7 @@ __global__ void __launch_bounds__(256) adamw_f32_kernel(float* __restrict__ P, c
   const float coef = clip ? clip_coef[0] : 1.f;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     const long long e0 = i * 4;
-    const int gi = find_group(groups, e0);
+    const int gi = fs_find_group(groups, e0);
     const AdamwGroup& G = groups.g[gi];
     if (e0 >= G.end) continue;
     float4 pv = reinterpret_cast<const float4*>(P)[i];
@@ -249,7 +237,7 @@ __global__ void __launch_bounds__(256) adamw_master_kernel(float* __restrict__ P
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = v0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += stride) {
     const long long e0 = i * 8;
-    const int gi = find_group(groups, e0);
+    const int gi = fs_find_group(groups, e0);
     const AdamwGroup& G = groups.g[gi];
     if (e0 >= G.end) continue;
     const bf8 gv = reinterpret_cast<const bf8*>(Gr)[i];
@@ -269,13 +257,7 @@ __global__ void __launch_bounds__(256) adamw_master_kernel(float* __restrict__ P
 }
 
 // ---- global grad norm ---------------------------------------------------------
-// chunk table: for each block, (tensor index, element begin, element end) in the flat store
-struct NormChunk { long long begin, end; int tensor; int pad; };
-
-template <typename T>
-__device__ __forceinline__ float ld_as_f(const T* p, long long i);
-template <> __device__ __forceinline__ float ld_as_f<bf16_t>(const bf16_t* p, long long i) { return bf2f(p[i]); }
-template <> __device__ __forceinline__ float ld_as_f<float>(const float* p, long long i) { return p[i]; }
+// chunk table (NormChunk, flat_store.h): for each block, (element begin, element end, tensor index) in the flat store
 
 // chunk_sq[blockIdx.x] = the chunk's sum of squares (one slot per chunk: no atomics, so the per-tensor sums below
 // add the chunks in a fixed order -- a double atomicAdd per chunk made the sum's last bits, and now and then the
@@ -317,7 +299,7 @@ __global__ void __launch_bounds__(256) grad_sqnorm_kernel(const T* __restrict__ 
     } else {
       float s = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { float f = ld_as_f<T>(G, e + j); s = fmaf(f, f, s); }
+      for (int j = 0; j < 8; ++j) { float f = fs_load1<T>(G, e + j); s = fmaf(f, f, s); }
       acc += s;
     }
   }
@@ -372,16 +354,8 @@ __global__ void clip_coef_kernel(const double* __restrict__ tensor_sq, int n_ten
 }
 
 // ---- C ABI ----------------------------------------------------------------------
-// workgroup cap of the update launches: OTAMD_ADAMW_BLOCKS (default: the whole chip).  An update overlapped with
-// the next forward on its own stream (util/optimizer/adamw_fused.py) holds only that many CUs' worth of slots.
-static long long adamw_max_blocks(long long dflt) {
-  static const long long cap = [] {
-    const char* e = getenv("OTAMD_ADAMW_BLOCKS");
-    return e ? atoll(e) : 0LL;
-  }();
-  return cap > 0 ? std::min(cap, dflt) : dflt;
-}
-
+// the LUT and the master launches honour the workgroup cap OTAMD_ADAMW_BLOCKS (fs_grid, flat_store.h; default: the
+// whole chip); the grids of adamw_grid do not
 static int adamw_grid(long long nvec) {
   long long blocks = (nvec + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
@@ -392,14 +366,10 @@ static int adamw_grid(long long nvec) {
 OTAMD_API int otamd_adamw_bf16_range(void* p, const void* g, void* m, void* v, long long begin, long long end,
                                      const AdamwGroup* groups, int n_groups, const float* clip_coef,
                                      int stochastic_rounding, unsigned long long seed, hipStream_t stream) {
-  if (!p || !g || !m || !v || begin < 0 || end < begin || (begin % 8) != 0 || (end % 8) != 0 || n_groups < 1 ||
-      n_groups > ADAMW_MAX_GROUPS)
-    return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return OTAMD_EINVAL;
+  if (!p || !g || !m || !v || !fs_window_ok(begin, end) || !fs_group_count_ok(n_groups)) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, g, m, v)) return OTAMD_EINVAL;
   if (end == begin) return OTAMD_OK;
-  AdamwGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  G.n = n_groups;
+  const AdamwGroups G = fs_groups_arg<AdamwGroups>(groups, n_groups);
   // LUT kernel when the denominator constants are shared (always, for one optimizer step with common
   // betas/eps) and the range is large enough to amortise the per-workgroup table.  OTAMD_ADAMW_LUT=0
   // forces the computed path, =1 the LUT with cached accesses, =2 the LUT with non-temporal accesses
@@ -413,7 +383,7 @@ OTAMD_API int otamd_adamw_bf16_range(void* p, const void* g, void* m, void* v, l
   if (const char* e = getenv("OTAMD_ADAMW_LUT")) { lut = shared && e[0] != '0'; nt = e[0] != '1'; }
   const long long v0 = begin / 8, v1 = end / 8;
   if (lut) {
-    const int blocks = (int)std::max(1LL, std::min<long long>((v1 - v0 + 1023) / 1024, adamw_max_blocks(512)));
+    const int blocks = fs_grid(v1 - v0, 1024, 512);
     if (nt)
       adamw_bf16_lut_kernel<true><<<blocks, 1024, 0, stream>>>((bf16_t*)p, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, v0,
                                                                v1, G, clip_coef, stochastic_rounding, seed);
@@ -437,12 +407,10 @@ OTAMD_API int otamd_adamw_bf16(void* p, const void* g, void* m, void* v, long lo
 
 OTAMD_API int otamd_adamw_f32(void* p, const void* g, void* m, void* v, long long n, const AdamwGroup* groups,
                               int n_groups, const float* clip_coef, hipStream_t stream) {
-  if (!p || !g || !m || !v || n < 0 || (n % 4) != 0 || n_groups < 1 || n_groups > ADAMW_MAX_GROUPS) return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return OTAMD_EINVAL;
+  if (!p || !g || !m || !v || n < 0 || (n % 4) != 0 || !fs_group_count_ok(n_groups)) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, g, m, v)) return OTAMD_EINVAL;
   if (n == 0) return OTAMD_OK;
-  AdamwGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  G.n = n_groups;
+  const AdamwGroups G = fs_groups_arg<AdamwGroups>(groups, n_groups);
   adamw_f32_kernel<<<adamw_grid(n / 4), 256, 0, stream>>>((float*)p, (const float*)g, (float*)m, (float*)v, n / 4, G,
                                                           clip_coef);
   OTAMD_CHECK_LAUNCH();
@@ -454,16 +422,13 @@ OTAMD_API int otamd_adamw_f32(void* p, const void* g, void* m, void* v, long lon
 OTAMD_API int otamd_adamw_master_range(void* p32, const void* g16, void* m32, void* v32, void* w16, long long begin,
                                        long long end, const AdamwGroup* groups, int n_groups, const float* clip_coef,
                                        hipStream_t stream) {
-  if (!p32 || !g16 || !m32 || !v32 || !w16 || begin < 0 || end < begin || (begin % 8) != 0 || (end % 8) != 0 ||
-      n_groups < 1 || n_groups > ADAMW_MAX_GROUPS)
+  if (!p32 || !g16 || !m32 || !v32 || !w16 || !fs_window_ok(begin, end) || !fs_group_count_ok(n_groups))
     return OTAMD_EINVAL;
-  if (((uintptr_t)p32 | (uintptr_t)g16 | (uintptr_t)m32 | (uintptr_t)v32 | (uintptr_t)w16) & 15) return OTAMD_EINVAL;
+  if (!fs_aligned16(p32, g16, m32, v32, w16)) return OTAMD_EINVAL;
   if (end == begin) return OTAMD_OK;
-  AdamwGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  G.n = n_groups;
+  const AdamwGroups G = fs_groups_arg<AdamwGroups>(groups, n_groups);
   const long long v0 = begin / 8, v1 = end / 8;
-  const int blocks = (int)std::max(1LL, std::min<long long>((v1 - v0 + 255) / 256, adamw_max_blocks(256 * 16)));
+  const int blocks = fs_grid(v1 - v0, 256, 256 * 16);
   adamw_master_kernel<<<blocks, 256, 0, stream>>>((float*)p32, (const bf16_t*)g16, (float*)m32, (float*)v32,
                                                   (bf16_t*)w16, v0, v1, G, clip_coef);
   OTAMD_CHECK_LAUNCH();
@@ -493,7 +458,7 @@ OTAMD_API int otamd_grad_clip_coef(const void* grads, int grad_dtype, const void
   return otamd_grad_clip_finalize(chunks, n_chunks, chunk_sq, tensor_sq, n_tensors, max_norm, grad_dtype, out, stream);
 }
 
-// the grad-norm pass split over the backward (util/optimizer/adamw_fused.OverlappedGradNorm): the squared norms of
+// the grad-norm pass split over the backward (util/optimizer/flat_store.OverlappedGradNorm): the squared norms of
 // chunks [c_begin, c_end) into their slots chunk_sq[c] as soon as those tensors' gradients are final, on the
 // weight-gradient stream beside the dgrad chain ...
 OTAMD_API int otamd_grad_sqnorm_chunks(const void* grads, int grad_dtype, const void* chunks, int c_begin, int c_end,
@@ -541,7 +506,7 @@ __global__ void scale_bf16_kernel(bf16_t* __restrict__ g, long long n8, const fl
   }
 }
 OTAMD_API int otamd_scale_bf16_by_device_scalar(void* g, long long n, const float* coef, hipStream_t stream) {
-  if (!g || !coef || (n % 8) != 0 || ((uintptr_t)g & 15)) return OTAMD_EINVAL;
+  if (!g || !coef || (n % 8) != 0 || !fs_aligned16(g)) return OTAMD_EINVAL;
   if (n == 0) return OTAMD_OK;
   scale_bf16_kernel<<<adamw_grid(n / 8), 256, 0, stream>>>((bf16_t*)g, n / 8, coef);
   OTAMD_CHECK_LAUNCH();

@@ -28,12 +28,8 @@
 //
 // HBM traffic per element, fp32 store: read p, g (8 B) and two codes, write p (4 B) and two codes: 16 B plus 16 B
 // of absmax per 256 elements, against 28 B of the fp32-state step in adamw.hip.
-#include "common.h"
+#include "flat_store.h"
 
-#include <algorithm>
-#include <cstdlib>
-
-#define A8_MAX_GROUPS 8
 #define A8_THREADS 256
 #define A8_BLOCK 256
 
@@ -52,7 +48,7 @@ struct A8Group {
   float pad;
 };
 struct A8Groups {
-  A8Group g[A8_MAX_GROUPS];
+  A8Group g[FS_MAX_GROUPS];
   int n;
 };
 
@@ -121,7 +117,7 @@ __global__ void __launch_bounds__(A8_THREADS)
   __syncthreads();
   const bool clip = clip_coef != nullptr;
   const float coef = clip ? clip_coef[0] : 1.f;
-  const uint32_t key = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t key = fs_seed_key(seed);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   const long long stride = (long long)gridDim.x * (A8_THREADS / 64);
@@ -220,8 +216,7 @@ OTAMD_API int otamd_adamw8bit_group_size(void) { return (int)sizeof(A8Group); }
 // n_absmax: entries of absmax1 / absmax2; n_f32: elements of m32 / v32.  Host code only: launches nothing.
 OTAMD_API int otamd_adamw8bit_check(const A8Seg* t, int n_segs, long long n, long long n_absmax, long long n_f32,
                                     int n_groups) {
-  if (!t || n_segs < 1 || n < 0 || (n % 8) != 0 || n_absmax < 0 || n_f32 < 0 || n_groups < 1 ||
-      n_groups > A8_MAX_GROUPS)
+  if (!t || n_segs < 1 || n < 0 || (n % 8) != 0 || n_absmax < 0 || n_f32 < 0 || !fs_group_count_ok(n_groups))
     return OTAMD_EINVAL;
   long long prev_end = 0, next_blk = 0, next_abs = 0, next_f32 = 0;
   for (int i = 0; i < n_segs; ++i) {
@@ -244,17 +239,6 @@ OTAMD_API int otamd_adamw8bit_check(const A8Seg* t, int n_segs, long long n, lon
   return OTAMD_OK;
 }
 
-// workgroup cap of the launch: OTAMD_ADAMW_BLOCKS, the cap adamw.hip honours
-static int a8_blocks(long long n_blocks) {
-  static const long long cap = [] {
-    const char* e = getenv("OTAMD_ADAMW_BLOCKS");
-    return e ? atoll(e) : 0LL;
-  }();
-  long long blocks = std::min<long long>((n_blocks + 3) / 4, 256 * 16);
-  if (cap > 0) blocks = std::min(blocks, cap);
-  return (int)std::max(1LL, blocks);
-}
-
 // form 0: p, g bf16; 1: p, g fp32; 2: p the fp32 master, g bf16, w16 its bf16 working copy.  code1 / code2: uint8,
 // n elements; absmax1 / absmax2: fp32, n_absmax; m32 / v32: fp32, n_f32 (may be null when n_f32 == 0); qmap: 512 fp32
 // on the device, the signed codebook then the unsigned one, each ascending.  table_dev / table_host: the same
@@ -265,32 +249,23 @@ OTAMD_API int otamd_adamw8bit_step(void* p, void* w16, const void* g, int form, 
                                    const void* table_host, int n_segs, const A8Group* groups, int n_groups,
                                    const float* clip_coef, int stochastic_rounding, unsigned long long seed,
                                    hipStream_t stream) {
-  if (!p || !g || !code1 || !code2 || !qmap || !table_dev || !table_host || !groups || form < 0 || form > 2 ||
-      (form == 2 && !w16))
+  if (!p || !g || !code1 || !code2 || !qmap || !table_dev || !table_host || !groups || !fs_form_ok(form, w16))
     return OTAMD_EINVAL;
   if ((n_absmax > 0 && (!absmax1 || !absmax2)) || (n_f32 > 0 && (!m32 || !v32))) return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)w16 | (uintptr_t)g | (uintptr_t)code1 | (uintptr_t)code2 | (uintptr_t)m32 |
-       (uintptr_t)v32) & 15)
-    return OTAMD_EINVAL;
+  if (!fs_aligned16(p, w16, g, code1, code2, m32, v32)) return OTAMD_EINVAL;
   const A8Seg* t = (const A8Seg*)table_host;
   if (const int rc = otamd_adamw8bit_check(t, n_segs, n, n_absmax, n_f32, n_groups)) return rc;
   const A8Seg& l = t[n_segs - 1];
   const long long n_blocks = l.blk0 + (l.end - l.begin + A8_BLOCK - 1) / A8_BLOCK;
-  A8Groups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  G.n = n_groups;
-  const int blocks = a8_blocks(n_blocks);
-#define A8_LAUNCH(TP, TG, FORM, WW, SR)                                                                              \
-  a8_step_kernel<TP, TG, FORM><<<blocks, A8_THREADS, 0, stream>>>(                                                   \
-      (TP*)p, WW, (const TG*)g, (uint8_t*)code1, (uint8_t*)code2, absmax1, absmax2, m32, v32, qmap,                  \
-      (const A8Seg*)table_dev, n_segs, n_blocks, G, clip_coef, SR, seed)
-  if (form == 0)
-    A8_LAUNCH(bf16_t, bf16_t, 0, nullptr, stochastic_rounding);
-  else if (form == 1)
-    A8_LAUNCH(float, float, 1, nullptr, 0);
-  else
-    A8_LAUNCH(float, bf16_t, 2, (bf16_t*)w16, 0);
-#undef A8_LAUNCH
+  const A8Groups G = fs_groups_arg<A8Groups>(groups, n_groups);
+  const int blocks = fs_grid(n_blocks, A8_THREADS / 64, 256 * 16);   // a wave per block; the cap adamw.hip honours
+  fs_dispatch(form, [&](auto F) {
+    using TP = typename decltype(F)::TP;
+    using TG = typename decltype(F)::TG;
+    a8_step_kernel<TP, TG, F.form><<<blocks, A8_THREADS, 0, stream>>>(
+        (TP*)p, F.w(w16), (const TG*)g, (uint8_t*)code1, (uint8_t*)code2, absmax1, absmax2, m32, v32, qmap,
+        (const A8Seg*)table_dev, n_segs, n_blocks, G, clip_coef, F.sr(stochastic_rounding), seed);
+  });
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

@@ -17,8 +17,9 @@
 //               decay, parameter write (bf16 RNE or stochastic, fp32, fp32 master + bf16 working copy)
 // Every reduction has a fixed order (no atomics): two runs give the same bits.
 //
-// Shared with adafactor.hip, in adafactor_walk.h: the unorm kernel of pass 4, the slab walk and the parameter write
-// of pass 9, the masked fp32 store, the EMA.  The statistics kernel of passes 1 and 6 restates af_stats_kernel's
+// Shared with adafactor.hip, in adafactor_walk.h: the unorm kernel of pass 4, the slab walk of pass 9, the EMA; with
+// every flat-store optimizer, in flat_store.h: the masked loads and stores and the parameter write of pass 9.  The
+// statistics kernel of passes 1 and 6 restates af_stats_kernel's
 // three-mode body (sharing it cost 0.4 ms a step through code placement).
 //
 // Tables.  The Adafactor tensor and slab tables, unchanged (adafactor_walk.h; adafactor.hip describes the three
@@ -46,7 +47,7 @@ struct CameGroup {
   float beta3, one_minus_beta3;   // instability factors
   int pad;
 };
-struct CameGroups { CameGroup g[AF_MAX_GROUPS]; };
+struct CameGroups { CameGroup g[FS_MAX_GROUPS]; };
 struct CameFold {
   long long i0, i1;   // kind 0: global rows b * rows + r; kind 1: global columns b * cols + c; kind 2: matrices
   int tensor;
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
   // pass 1, one vector: x = u_c - m, m written
   auto moment = [&](long long v, const float* g, const float* fac, unsigned valid, float* x) {
     float m[8];
-    af_load8<float>(M, v, m);
+    fs_load8<float>(M, v, m);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float u = fac[j] * g[j];
@@ -95,12 +96,12 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
       m[j] = fmaf(u, G.one_minus_beta1, m[j] * G.beta1);   // exp_avg.mul_(beta1).add_(update, alpha=1 - beta1)
       x[j] = u - m[j];
     }
-    af_store8(M, v, m, valid);
+    fs_store8(M, v, m, valid);
   };
 
   if (T.mode == 0) {
     for (long long i = sl.row0 + tid; i < sl.row1; i += AF_THREADS) {
-      const float g = af_clip<BFROUND>(af_load1<TG>(Gr, T.offset + i), coef, clip);
+      const float g = fs_clip<BFROUND>(fs_load1<TG>(Gr, T.offset + i), coef, clip);
       if constexpr (PASS == 0) {
         float* v = state + T.full_off + i;
         *v = af_ema(*v, g * g + eps, beta, omb);
@@ -128,9 +129,9 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
       }
       for (long long v = a0 + 8 * tid; v < e1; v += 8 * AF_THREADS) {
         float f[8];
-        af_load8<TG>(Gr, v, f);
+        fs_load8<TG>(Gr, v, f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = af_clip<BFROUND>(f[j], coef, clip);
+        for (int j = 0; j < 8; ++j) f[j] = fs_clip<BFROUND>(f[j], coef, clip);
         if constexpr (PASS == 1) {
           float fac[8], x[8];
           const int j0 = v < e0 ? (int)(e0 - v) : 0;
@@ -211,9 +212,9 @@ __global__ void __launch_bounds__(AF_THREADS) came_stats_kernel(const TG* __rest
         const long long v = (e0 & ~7LL) + 8 * j;
         if (v < e1) {
           float f[8];
-          af_load8<TG>(Gr, v, f);
+          fs_load8<TG>(Gr, v, f);
 #pragma unroll
-          for (int jj = 0; jj < 8; ++jj) f[jj] = af_clip<BFROUND>(f[jj], coef, clip);
+          for (int jj = 0; jj < 8; ++jj) f[jj] = fs_clip<BFROUND>(f[jj], coef, clip);
           if constexpr (PASS == 1) {
             float fac[8], x[8];
             const float rf = af_rsqrt(fstate[T.row_off + r0 + i] / rmean);
@@ -329,13 +330,13 @@ __global__ void __launch_bounds__(AF_THREADS) came_apply_kernel(TP* __restrict__
   const AdafactorSlab sl = slabs[s0 + blockIdx.x];
   const AdafactorTensor T = tensors[sl.tensor];
   const CameGroup G = groups.g[T.group];
-  const uint32_t k = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t k = fs_seed_key(seed);
   const float lr = G.lr, alpha = G.alpha_wd;
   const bool decay = alpha != 0.f;
   // m: the new first moment; fac: the instability factors (1 for unfactored tensors)
   auto body = [&](long long v, const float* m, const float* fac, unsigned valid) {
     float p[8];
-    af_load8<TP>(P, v, p);
+    fs_load8<TP>(P, v, p);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float u = fac[j] * m[j];   // res_approx.mul_(exp_avg)
@@ -348,13 +349,13 @@ __global__ void __launch_bounds__(AF_THREADS) came_apply_kernel(TP* __restrict__
       }
       p[j] = x - u;              // p.add_(-update)
     }
-    af_write_params<FORM>(P, W, v, p, valid, sr, k);
+    fs_write_params<FORM>(P, W, v, p, valid, sr, k);
   };
   if (T.mode == 0) {   // update = exp_avg
     const long long e0 = T.offset + sl.row0, e1 = T.offset + sl.row1;
     for (long long v = (e0 & ~7LL) + 8 * threadIdx.x; v < e1; v += 8 * AF_THREADS) {
       float m[8], fac[8];
-      af_load8<float>(M, v, m);
+      fs_load8<float>(M, v, m);
       unsigned valid = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -442,24 +443,18 @@ OTAMD_API int otamd_came_step(void* p, const void* g, void* w16, int form, float
                               const float* clip_coef, int stochastic_rounding, unsigned long long seed,
                               hipStream_t stream) {
   if (!p || !g || !m || !state_sq || !state_res || !scratch_sq || !scratch_res || !slab_sq || !scal || !tensors ||
-      !slabs || !fold || !groups || form < 0 || form > 2 || (form == 2 && !w16) || n_groups < 1 ||
-      n_groups > AF_MAX_GROUPS || t_begin < 0 || t_end < t_begin || s_begin < 0 || s_end < s_begin || f_begin < 0 ||
-      f_end < f_begin || r_begin < 0 || r_end < r_begin)
+      !slabs || !fold || !groups || !fs_form_ok(form, w16) || !fs_group_count_ok(n_groups) || t_begin < 0 ||
+      t_end < t_begin || s_begin < 0 || s_end < s_begin || f_begin < 0 || f_end < f_begin || r_begin < 0 ||
+      r_end < r_begin)
     return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)w16 | (uintptr_t)m | (uintptr_t)state_sq | (uintptr_t)state_res |
-       (uintptr_t)scratch_sq | (uintptr_t)scratch_res) & 15)
-    return OTAMD_EINVAL;
+  if (!fs_aligned16(p, g, w16, m, state_sq, state_res, scratch_sq, scratch_res)) return OTAMD_EINVAL;
   if (t_end == t_begin || s_end == s_begin) return OTAMD_OK;
-  CameGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  CameArgs a = {p, g, nullptr, m, state_sq, state_res, scratch_sq, scratch_res, slab_sq, scal,
-                (const AdafactorTensor*)tensors, (const AdafactorSlab*)slabs, (const CameFold*)fold,
-                t_begin, t_end, s_begin, s_end, f_begin, f_end, r_begin, r_end, clip_coef, 0, seed};
-  if (form == 0) {
-    a.sr = stochastic_rounding;
-    return came_launch<bf16_t, bf16_t, 0>(a, G, stream);
-  }
-  if (form == 1) return came_launch<float, float, 1>(a, G, stream);
-  a.w = w16;
-  return came_launch<float, bf16_t, 2>(a, G, stream);
+  const CameGroups G = fs_groups_arg<CameGroups>(groups, n_groups);
+  return fs_dispatch(form, [&](auto F) {
+    const CameArgs a = {p, g, F.w(w16), m, state_sq, state_res, scratch_sq, scratch_res, slab_sq, scal,
+                        (const AdafactorTensor*)tensors, (const AdafactorSlab*)slabs, (const CameFold*)fold,
+                        t_begin, t_end, s_begin, s_end, f_begin, f_end, r_begin, r_end, clip_coef,
+                        F.sr(stochastic_rounding), seed};
+    return came_launch<typename decltype(F)::TP, typename decltype(F)::TG, F.form>(a, G, stream);
+  });
 }

@@ -17,9 +17,7 @@
 // non-temporal accesses for the shadow (touched once per update); the parameters are read with the default policy,
 // the optimizer has just written them and the next forward reads them.  The kernels need no group table and run over
 // the store's padding too: padding is 0 in both buffers and 0 + omd * (0 - 0) stays 0.
-#include "common.h"
-
-#include <algorithm>
+#include "flat_store.h"
 
 // 1024-thread workgroups, two per CU (256 CUs), a grid-stride loop over the rest, two granules per thread and sweep.
 // Measured on MI355X over 2.567 G elements, hipEvents, median of 10 (the fused AdamW's 14 B per element in the same
@@ -156,9 +154,8 @@ OTAMD_API int otamd_ema_sweep_elems(int form) {
 // ema, p: flat buffers of the same layout; [begin, end): element range (multiples of 8); form 0 / 1 / 2 as above
 OTAMD_API int otamd_ema_range(void* ema, const void* p, int form, long long begin, long long end,
                               float one_minus_decay, hipStream_t stream) {
-  if (!ema || !p || form < 0 || form > 2 || begin < 0 || end < begin || (begin % 8) != 0 || (end % 8) != 0)
-    return OTAMD_EINVAL;
-  if (((uintptr_t)ema | (uintptr_t)p) & 15) return OTAMD_EINVAL;
+  if (!ema || !p || form < 0 || form > 2 || !fs_window_ok(begin, end)) return OTAMD_EINVAL;
+  if (!fs_aligned16(ema, p)) return OTAMD_EINVAL;
   if (end == begin) return OTAMD_OK;
   const long long u0 = begin / ema_unit(form), u1 = end / ema_unit(form);
   const long long threads = (u1 - u0 + EMA_UNROLL - 1) / EMA_UNROLL;

@@ -22,7 +22,7 @@
 //   prodigy_apply       grid-stride over the store (workgroup cap OTAMD_ADAMW_BLOCKS, as adamw.hip):
 //                         p = p + (-weight_decay dlr) p                    (decoupled decay)
 //                         p = p - dlr m / (sqrt(v) + d eps)                new d, old dlr; beta1 == 0: d g for m
-//                       written through af_write_params (fp32; fp32 master + RNE bf16 working copy; bf16 RNE or stochastic).
+//                       written through fs_write_params (flat_store.h: fp32; fp32 master + RNE bf16 working copy; bf16 RNE or stochastic).
 //
 // Numerics: m, v, s and p0 are fp32 for every store form; every fp32 operation above is one rounding, in the order
 // written (t = a * b; r = t + c: no fused multiply-add), so compile with -ffp-contract=off.  The per-element
@@ -31,15 +31,11 @@
 // HBM traffic per fp32 element: accumulate reads p, g, p0, m, v, s (24 B) and writes m, v, s (12 B); apply reads
 // p, m, v (12 B) and writes p (4 B).  A master store reads g as bf16 (-2 B) and also writes the bf16 working copy
 // (+2 B); a bf16 store reads and writes p and g as bf16.  The first step writes p0 instead of reading it.
-#include "adafactor_walk.h"
+#include "flat_store.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 #define PRODIGY_THREADS 256
-
-struct NormChunk { long long begin, end; int tensor; int pad; };   // the chunk table of adamw.hip
 
 struct ProdigyState {   // device resident; the host writes it at start-up and on load_state_dict only
   double d, d_max, d_numerator, d_denom, d_hat;
@@ -63,7 +59,7 @@ __device__ __forceinline__ double prodigy_dlr(double d, double k, const ProdigyH
 // g after the pending clip and, for the coupled form of weight decay, g + weight_decay p
 template <bool BFROUND>
 __device__ __forceinline__ float prodigy_grad(float g, float p, float coef, bool clip, float wd_coupled) {
-  g = af_clip<BFROUND>(g, coef, clip);
+  g = fs_clip<BFROUND>(g, coef, clip);
   if (wd_coupled != 0.f) {
     const float t = wd_coupled * p;
     g = g + t;
@@ -96,12 +92,12 @@ __global__ void __launch_bounds__(PRODIGY_THREADS)
   double num = 0.0, den = 0.0;
   for (long long e = c.begin + 8 * threadIdx.x; e < c.end; e += 8 * PRODIGY_THREADS) {
     float p[8], g[8], p0[8], m[8], v[8], s[8];
-    af_load8<TP>(P, e, p);
-    af_load8<TG>(Gr, e, g);
-    if (!capture) af_load8<float>(P0, e, p0);
-    if (has_m) af_load8<float>(M, e, m);
-    af_load8<float>(V, e, v);
-    af_load8<float>(Sx, e, s);
+    fs_load8<TP>(P, e, p);
+    fs_load8<TG>(Gr, e, g);
+    if (!capture) fs_load8<float>(P0, e, p0);
+    if (has_m) fs_load8<float>(M, e, m);
+    fs_load8<float>(V, e, v);
+    fs_load8<float>(Sx, e, s);
     const unsigned valid = e + 8 <= c.end ? 0xFFu : (1u << (int)(c.end - e)) - 1u;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -124,10 +120,10 @@ __global__ void __launch_bounds__(PRODIGY_THREADS)
       s[j] = t5 + t6;
       den += ok ? (double)fabsf(s[j]) : 0.0;
     }
-    if (capture) af_store8(P0, e, p0, valid);
-    if (has_m) af_store8(M, e, m, valid);
-    af_store8(V, e, v, valid);
-    af_store8(Sx, e, s, valid);
+    if (capture) fs_store8(P0, e, p0, valid);
+    if (has_m) fs_store8(M, e, m, valid);
+    fs_store8(V, e, v, valid);
+    fs_store8(Sx, e, s, valid);
   }
   num = wave_sum_d(num);
   den = wave_sum_d(den);
@@ -197,7 +193,7 @@ __global__ void __launch_bounds__(PRODIGY_THREADS)
                          unsigned long long seed) {
   if (S->skip != 0.0) return;
   const double d = S->d, dlr = S->dlr;
-  const uint32_t k = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t k = fs_seed_key(seed);
   const bool has_m = H.beta1 > 0.0;
   const bool clip = clip_coef != nullptr;
   const float coef = clip ? clip_coef[0] : 1.f;
@@ -208,13 +204,13 @@ __global__ void __launch_bounds__(PRODIGY_THREADS)
   for (long long i = blockIdx.x * (long long)PRODIGY_THREADS + threadIdx.x; i < n8; i += stride) {
     const long long e = i * 8;
     float p[8], m[8], v[8];
-    af_load8<TP>(P, e, p);
-    af_load8<float>(V, e, v);
+    fs_load8<TP>(P, e, p);
+    fs_load8<float>(V, e, v);
     if (has_m) {
-      af_load8<float>(M, e, m);
+      fs_load8<float>(M, e, m);
     } else {   // beta1 == 0: d g stands for the first moment (g as accumulate saw it: p is still the old one)
       float g[8];
-      af_load8<TG>(Gr, e, g);
+      fs_load8<TG>(Gr, e, g);
 #pragma unroll
       for (int j = 0; j < 8; ++j) m[j] = df * prodigy_grad<FORM == 0>(g[j], p[j], coef, clip, wdc);
     }
@@ -229,22 +225,13 @@ __global__ void __launch_bounds__(PRODIGY_THREADS)
       const float u = (dlrf * m[j]) / denom;
       p[j] = x - u;
     }
-    af_write_params<FORM>(P, W, e, p, 0xFFu, sr, k);
+    fs_write_params<FORM>(P, W, e, p, 0xFFu, sr, k);
   }
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------
 OTAMD_API int otamd_prodigy_state_size(void) { return (int)sizeof(ProdigyState); }
 OTAMD_API int otamd_prodigy_hyper_size(void) { return (int)sizeof(ProdigyHyper); }
-
-// workgroup cap of the apply launch: OTAMD_ADAMW_BLOCKS, the cap adamw.hip honours
-static long long prodigy_max_blocks(long long dflt) {
-  static const long long cap = [] {
-    const char* e = getenv("OTAMD_ADAMW_BLOCKS");
-    return e ? atoll(e) : 0LL;
-  }();
-  return cap > 0 ? std::min(cap, dflt) : dflt;
-}
 
 static bool prodigy_hyper_ok(const ProdigyHyper* h) {
   return h && h->d0 > 0.0 && h->eps > 0.0 && h->beta1 >= 0.0 && h->beta1 < 1.0 && h->beta2 >= 0.0 && h->beta2 < 1.0 &&
@@ -261,20 +248,15 @@ OTAMD_API int otamd_prodigy_accumulate(const void* p, const void* g, int form, f
   if (!p || !g || !p0 || !v || !s || !chunks || !chunk_num || !chunk_den || !state || form < 0 || form > 2 ||
       n_chunks < 0 || !prodigy_hyper_ok(hyper) || (hyper->beta1 > 0.0 && !m))
     return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)p0 | (uintptr_t)m | (uintptr_t)v | (uintptr_t)s) & 15) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, g, p0, m, v, s)) return OTAMD_EINVAL;
   if (n_chunks == 0) return OTAMD_OK;
-  const NormChunk* c = (const NormChunk*)chunks;
-  const ProdigyState* S = (const ProdigyState*)state;
-  const ProdigyHyper H = *hyper;
-  if (form == 0)
-    prodigy_accumulate_kernel<bf16_t, bf16_t, true><<<n_chunks, PRODIGY_THREADS, 0, stream>>>(
-        (const bf16_t*)p, (const bf16_t*)g, p0, m, v, s, c, chunk_num, chunk_den, S, H, clip_coef, capture_p0);
-  else if (form == 1)
-    prodigy_accumulate_kernel<float, float, false><<<n_chunks, PRODIGY_THREADS, 0, stream>>>(
-        (const float*)p, (const float*)g, p0, m, v, s, c, chunk_num, chunk_den, S, H, clip_coef, capture_p0);
-  else
-    prodigy_accumulate_kernel<float, bf16_t, false><<<n_chunks, PRODIGY_THREADS, 0, stream>>>(
-        (const float*)p, (const bf16_t*)g, p0, m, v, s, c, chunk_num, chunk_den, S, H, clip_coef, capture_p0);
+  fs_dispatch(form, [&](auto F) {
+    using TP = typename decltype(F)::TP;
+    using TG = typename decltype(F)::TG;
+    prodigy_accumulate_kernel<TP, TG, F.form == 0><<<n_chunks, PRODIGY_THREADS, 0, stream>>>(
+        (const TP*)p, (const TG*)g, p0, m, v, s, (const NormChunk*)chunks, chunk_num, chunk_den,
+        (const ProdigyState*)state, *hyper, clip_coef, capture_p0);
+  });
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }
@@ -294,25 +276,20 @@ OTAMD_API int otamd_prodigy_finalize(const double* chunk_num, const double* chun
 OTAMD_API int otamd_prodigy_apply(void* p, void* w16, const void* g, int form, const float* m, const float* v,
                                   long long n, const void* state, const ProdigyHyper* hyper, const float* clip_coef,
                                   int stochastic_rounding, unsigned long long seed, hipStream_t stream) {
-  if (!p || !g || !v || !state || form < 0 || form > 2 || (form == 2 && !w16) || n < 0 || (n % 8) != 0 ||
-      !prodigy_hyper_ok(hyper) || (hyper->beta1 > 0.0 && !m))
+  if (!p || !g || !v || !state || !fs_form_ok(form, w16) || n < 0 || (n % 8) != 0 || !prodigy_hyper_ok(hyper) ||
+      (hyper->beta1 > 0.0 && !m))
     return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)w16 | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, w16, g, m, v)) return OTAMD_EINVAL;
   if (n == 0) return OTAMD_OK;
   const long long n8 = n / 8;
-  const int blocks = (int)std::max(1LL, std::min<long long>((n8 + PRODIGY_THREADS - 1) / PRODIGY_THREADS,
-                                                             prodigy_max_blocks(256 * 16)));
-  const ProdigyState* S = (const ProdigyState*)state;
-  const ProdigyHyper H = *hyper;
-  if (form == 0)
-    prodigy_apply_kernel<bf16_t, bf16_t, 0><<<blocks, PRODIGY_THREADS, 0, stream>>>(
-        (bf16_t*)p, nullptr, m, v, (const bf16_t*)g, n8, S, H, clip_coef, stochastic_rounding, seed);
-  else if (form == 1)
-    prodigy_apply_kernel<float, float, 1><<<blocks, PRODIGY_THREADS, 0, stream>>>(
-        (float*)p, nullptr, m, v, (const float*)g, n8, S, H, clip_coef, 0, seed);
-  else
-    prodigy_apply_kernel<float, bf16_t, 2><<<blocks, PRODIGY_THREADS, 0, stream>>>(
-        (float*)p, (bf16_t*)w16, m, v, (const bf16_t*)g, n8, S, H, clip_coef, 0, seed);
+  const int blocks = fs_grid(n8, PRODIGY_THREADS, 256 * 16);   // the cap adamw.hip honours
+  fs_dispatch(form, [&](auto F) {
+    using TP = typename decltype(F)::TP;
+    using TG = typename decltype(F)::TG;
+    prodigy_apply_kernel<TP, TG, F.form><<<blocks, PRODIGY_THREADS, 0, stream>>>(
+        (TP*)p, F.w(w16), m, v, (const TG*)g, n8, (const ProdigyState*)state, *hyper, clip_coef,
+        F.sr(stochastic_rounding), seed);
+  });
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

@@ -14,7 +14,7 @@
 //               y  = y + ckp1 (z - y);   y = y + a_y gn;   z = z - lr gn
 //             On a group's first step z = y is taken from the parameters instead of read.
 //   sf_swap   p = p + w (z - p) over group ranges: w = 1 - 1/beta1 turns y into x, w = 1 - beta1 turns x into y.
-// Both write the parameters through af_write_params (adafactor_walk.h): fp32; fp32 master + its RNE bf16 working copy;
+// Both write the parameters through fs_write_params (flat_store.h): fp32; fp32 master + its RNE bf16 working copy;
 // bf16 RNE or stochastic (the swap always RNE: a mode switch must be repeatable).
 //
 // Numerics: every fp32 operation above is one rounding in the order written (t = a * b; r = t + c: no fused
@@ -23,12 +23,8 @@
 // HBM traffic per element: read y, g, z, v and write y, z, v -- AdamW's bytes on the fp32 and master forms (16 + 12 B,
 // master 14 + 14 B); a bf16 store keeps z and v in fp32 (12 + 10 B against AdamW's 8 + 6 B).  The first step does not
 // read z.  No atomics, no reductions.
-#include "adafactor_walk.h"
+#include "flat_store.h"
 
-#include <algorithm>
-#include <cstdlib>
-
-#define SF_MAX_GROUPS 8
 #define SF_THREADS 256
 
 struct SfGroup {
@@ -45,7 +41,7 @@ struct SfGroup {
   int pad;
 };
 struct SfGroups {
-  SfGroup g[SF_MAX_GROUPS];
+  SfGroup g[FS_MAX_GROUPS];
   int n;
 };
 struct SfSwapGroup {
@@ -54,25 +50,9 @@ struct SfSwapGroup {
   int pad;
 };
 struct SfSwapGroups {
-  SfSwapGroup g[SF_MAX_GROUPS];
+  SfSwapGroup g[FS_MAX_GROUPS];
   int n;
 };
-
-template <typename GS>
-__device__ __forceinline__ int sf_find_group(const GS& G, long long e) {
-  int gi = 0;
-#pragma unroll
-  for (int i = 1; i < SF_MAX_GROUPS; ++i)
-    if (i < G.n && e >= G.g[i].begin) gi = i;
-  return gi;
-}
-
-// lanes of the vector at e0 that belong to [begin, end) (tensors start on vectors, so begin <= e0 here; the mask
-// keeps the store's padding, which belongs to no group, untouched)
-__device__ __forceinline__ unsigned sf_valid(long long e0, long long begin, long long end) {
-  if (e0 < begin || e0 >= end) return 0u;
-  return e0 + 8 <= end ? 0xFFu : (1u << (int)(end - e0)) - 1u;
-}
 
 // FORM 0: bf16 store (RNE or stochastic); 1: fp32 store; 2: fp32 master P + bf16 working copy W = rne(master).
 // [v0, v1): the 8-element vectors of the launch window, global indices.  FIRST: the first step (every group's flag;
@@ -85,21 +65,21 @@ __global__ void __launch_bounds__(SF_THREADS)
                    const float* __restrict__ clip_coef, int sr, unsigned long long seed) {
   const bool clip = clip_coef != nullptr;
   const float coef = clip ? clip_coef[0] : 1.f;
-  const uint32_t key = (uint32_t)(seed ^ (seed >> 32));
+  const uint32_t key = fs_seed_key(seed);
   const long long stride = (long long)gridDim.x * SF_THREADS;
   for (long long i = v0 + blockIdx.x * (long long)SF_THREADS + threadIdx.x; i < v1; i += stride) {
     const long long e0 = i * 8;
     float y[8], g[8], z[8], v[8];
-    af_load8<TP>(P, e0, y);
-    af_load8<TG>(Gr, e0, g);
-    af_load8<float>(V, e0, v);
-    if constexpr (!FIRST) af_load8<float>(Z, e0, z);
-    const SfGroup& G = groups.g[sf_find_group(groups, e0)];
-    const unsigned valid = sf_valid(e0, G.begin, G.end);
+    fs_load8<TP>(P, e0, y);
+    fs_load8<TG>(Gr, e0, g);
+    fs_load8<float>(V, e0, v);
+    if constexpr (!FIRST) fs_load8<float>(Z, e0, z);
+    const SfGroup& G = groups.g[fs_find_group(groups, e0)];
+    const unsigned valid = fs_valid(e0, G.begin, G.end);
     if (valid == 0u) continue;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float gg = af_clip<FORM == 0>(g[j], coef, clip);
+      const float gg = fs_clip<FORM == 0>(g[j], coef, clip);
       const float zz = FIRST ? y[j] : z[j];
       const float t1 = G.beta2 * v[j], t2 = (G.one_minus_beta2 * gg) * gg;
       v[j] = t1 + t2;
@@ -115,9 +95,9 @@ __global__ void __launch_bounds__(SF_THREADS)
       z[j] = zz - t5;
       y[j] = yy;
     }
-    af_store8(V, e0, v, valid);
-    af_store8(Z, e0, z, valid);
-    af_write_params<FORM>(P, W, e0, y, valid, sr, key);
+    fs_store8(V, e0, v, valid);
+    fs_store8(Z, e0, z, valid);
+    fs_write_params<FORM>(P, W, e0, y, valid, sr, key);
   }
 }
 
@@ -129,10 +109,10 @@ __global__ void __launch_bounds__(SF_THREADS)
   for (long long i = v0 + blockIdx.x * (long long)SF_THREADS + threadIdx.x; i < v1; i += stride) {
     const long long e0 = i * 8;
     float p[8], z[8];
-    af_load8<TP>(P, e0, p);
-    af_load8<float>(Z, e0, z);
-    const SfSwapGroup& G = groups.g[sf_find_group(groups, e0)];
-    const unsigned valid = sf_valid(e0, G.begin, G.end);
+    fs_load8<TP>(P, e0, p);
+    fs_load8<float>(Z, e0, z);
+    const SfSwapGroup& G = groups.g[fs_find_group(groups, e0)];
+    const unsigned valid = fs_valid(e0, G.begin, G.end);
     if (valid == 0u) continue;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -140,7 +120,7 @@ __global__ void __launch_bounds__(SF_THREADS)
       const float t = G.w * d;
       p[j] = p[j] + t;
     }
-    af_write_params<FORM>(P, W, e0, p, valid, 0, 0u);
+    fs_write_params<FORM>(P, W, e0, p, valid, 0, 0u);
   }
 }
 
@@ -148,33 +128,8 @@ __global__ void __launch_bounds__(SF_THREADS)
 OTAMD_API int otamd_sf_group_size(void) { return (int)sizeof(SfGroup); }
 OTAMD_API int otamd_sf_swap_group_size(void) { return (int)sizeof(SfSwapGroup); }
 
-// workgroup cap of the launches: OTAMD_ADAMW_BLOCKS, the cap adamw.hip honours
-static int sf_blocks(long long nvec) {
-  static const long long cap = [] {
-    const char* e = getenv("OTAMD_ADAMW_BLOCKS");
-    return e ? atoll(e) : 0LL;
-  }();
-  long long blocks = std::min<long long>((nvec + SF_THREADS - 1) / SF_THREADS, 256 * 16);
-  if (cap > 0) blocks = std::min(blocks, cap);
-  return (int)std::max(1LL, blocks);
-}
-
-// groups sorted by begin, disjoint, inside [0, n), begin on a vector
-template <typename G>
-static bool sf_groups_ok(const G* groups, int n_groups, long long n) {
-  if (!groups || n_groups < 1 || n_groups > SF_MAX_GROUPS) return false;
-  long long prev = 0;
-  for (int i = 0; i < n_groups; ++i) {
-    if (groups[i].begin < prev || groups[i].end < groups[i].begin || groups[i].end > n || (groups[i].begin % 8) != 0)
-      return false;
-    prev = groups[i].end;
-  }
-  return true;
-}
-
-static bool sf_window_ok(long long n, long long begin, long long end) {
-  return n >= 0 && (n % 8) == 0 && begin >= 0 && begin <= end && end <= n && (begin % 8) == 0 && (end % 8) == 0;
-}
+// workgroups of a launch over nvec vectors, under the cap adamw.hip honours (fs_grid, flat_store.h)
+static int sf_blocks(long long nvec) { return fs_grid(nvec, SF_THREADS, 256 * 16); }
 
 // form 0: p, g bf16; 1: p, g fp32; 2: p the fp32 master, g bf16, w16 its bf16 working copy.  z / v: fp32, indexed as
 // the store.  n: elements of the store (a multiple of 8); [begin, end): the window of this launch, multiples of 8.
@@ -182,57 +137,41 @@ OTAMD_API int otamd_sf_adamw_step(void* p, void* w16, const void* g, int form, f
                                   long long begin, long long end, const SfGroup* groups, int n_groups,
                                   const float* clip_coef, int stochastic_rounding, unsigned long long seed,
                                   hipStream_t stream) {
-  if (!p || !g || !z || !v || form < 0 || form > 2 || (form == 2 && !w16) || !sf_window_ok(n, begin, end) ||
-      !sf_groups_ok(groups, n_groups, n))
+  if (!p || !g || !z || !v || !fs_form_ok(form, w16) || !fs_window_ok(n, begin, end) ||
+      !fs_groups_ok(groups, n_groups, n))
     return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)w16 | (uintptr_t)g | (uintptr_t)z | (uintptr_t)v) & 15) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, w16, g, z, v)) return OTAMD_EINVAL;
   if (end == begin) return OTAMD_OK;
-  SfGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  G.n = n_groups;
+  const SfGroups G = fs_groups_arg<SfGroups>(groups, n_groups);
   for (int i = 1; i < n_groups; ++i)
     if ((groups[i].first != 0) != (groups[0].first != 0)) return OTAMD_EINVAL;   // one first step for the whole store
   const long long v0 = begin / 8, v1 = end / 8;
   const int blocks = sf_blocks(v1 - v0);
   const bool first = groups[0].first != 0;
-#define SF_LAUNCH(TP, TG, FORM, PP, WW, SR)                                                                          \
-  do {                                                                                                               \
-    if (first)                                                                                                       \
-      sf_step_kernel<TP, TG, FORM, true><<<blocks, SF_THREADS, 0, stream>>>((TP*)PP, WW, (const TG*)g, z, v, v0, v1, \
-                                                                            G, clip_coef, SR, seed);                 \
-    else                                                                                                             \
-      sf_step_kernel<TP, TG, FORM, false><<<blocks, SF_THREADS, 0, stream>>>((TP*)PP, WW, (const TG*)g, z, v, v0,    \
-                                                                             v1, G, clip_coef, SR, seed);            \
-  } while (0)
-  if (form == 0)
-    SF_LAUNCH(bf16_t, bf16_t, 0, p, nullptr, stochastic_rounding);
-  else if (form == 1)
-    SF_LAUNCH(float, float, 1, p, nullptr, 0);
-  else
-    SF_LAUNCH(float, bf16_t, 2, p, (bf16_t*)w16, 0);
-#undef SF_LAUNCH
+  fs_dispatch(form, [&](auto F) {
+    using TP = typename decltype(F)::TP;
+    using TG = typename decltype(F)::TG;
+    auto* kernel = first ? sf_step_kernel<TP, TG, F.form, true> : sf_step_kernel<TP, TG, F.form, false>;
+    kernel<<<blocks, SF_THREADS, 0, stream>>>((TP*)p, F.w(w16), (const TG*)g, z, v, v0, v1, G, clip_coef,
+                                              F.sr(stochastic_rounding), seed);
+  });
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }
 
 OTAMD_API int otamd_sf_swap(void* p, void* w16, int form, const float* z, long long n, long long begin, long long end,
                             const SfSwapGroup* groups, int n_groups, hipStream_t stream) {
-  if (!p || !z || form < 0 || form > 2 || (form == 2 && !w16) || !sf_window_ok(n, begin, end) ||
-      !sf_groups_ok(groups, n_groups, n))
+  if (!p || !z || !fs_form_ok(form, w16) || !fs_window_ok(n, begin, end) || !fs_groups_ok(groups, n_groups, n))
     return OTAMD_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)w16 | (uintptr_t)z) & 15) return OTAMD_EINVAL;
+  if (!fs_aligned16(p, w16, z)) return OTAMD_EINVAL;
   if (end == begin) return OTAMD_OK;
-  SfSwapGroups G = {};
-  for (int i = 0; i < n_groups; ++i) G.g[i] = groups[i];
-  G.n = n_groups;
+  const SfSwapGroups G = fs_groups_arg<SfSwapGroups>(groups, n_groups);
   const long long v0 = begin / 8, v1 = end / 8;
   const int blocks = sf_blocks(v1 - v0);
-  if (form == 0)
-    sf_swap_kernel<bf16_t, 0><<<blocks, SF_THREADS, 0, stream>>>((bf16_t*)p, nullptr, z, v0, v1, G);
-  else if (form == 1)
-    sf_swap_kernel<float, 1><<<blocks, SF_THREADS, 0, stream>>>((float*)p, nullptr, z, v0, v1, G);
-  else
-    sf_swap_kernel<float, 2><<<blocks, SF_THREADS, 0, stream>>>((float*)p, (bf16_t*)w16, z, v0, v1, G);
+  fs_dispatch(form, [&](auto F) {
+    using TP = typename decltype(F)::TP;
+    sf_swap_kernel<TP, F.form><<<blocks, SF_THREADS, 0, stream>>>((TP*)p, F.w(w16), z, v0, v1, G);
+  });
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

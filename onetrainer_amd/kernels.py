@@ -839,13 +839,55 @@ def conv2d_wgrad(dy: torch.Tensor, x: torch.Tensor, ksize=3, stride=1, pad=1, up
 
 # ------------------------------------------------------------------------------------------
 # optimizer
+def store_form(p, g, w, who) -> int:
+    """the C-ABI form code of the flat-store optimizers (csrc/flat_store.h): 0 bf16 store, 1 fp32 store, 2 fp32 master p
+    with bf16 gradients and the bf16 working copy w.  g: the gradients, or None for a launch that reads none."""
+    if w is not None:
+        _req(p.dtype == F32 and w.dtype == BF16 and (g is None or g.dtype == BF16), f"{who} master: fp32 p, bf16 g and w")
+        return 2
+    _req(p.dtype in (BF16, F32) and (g is None or g.dtype == p.dtype),
+         f"{who}: a bf16 or fp32 store with gradients in its dtype")
+    return 0 if p.dtype == BF16 else 1
+
+
+def _flat_checks(who, n, same, f32=()):
+    """same: buffers in the store's layout whatever their dtype (None entries are skipped); f32: fp32 states indexed
+    as the store.  n: the store's elements, a multiple of 8."""
+    for t in same:
+        _req(t is None or (t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t)),
+             f"{who} flat buffers")
+    for t in f32:
+        _req(t is None or (t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == n and _aligned(t)),
+             f"{who} fp32 states, indexed as the store")
+
+
+def _window_checks(who, n, begin, end, groups=None, ranges=False) -> int:
+    """the launch window [begin, end) of a store of n elements (end None: n) and the parameter groups: one to eight,
+    with `ranges` sorted, disjoint element ranges that begin on a vector.  Returns end."""
+    end = n if end is None else end
+    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0, f"{who} range: multiples of 8 within the store")
+    if groups is not None:
+        _req(1 <= len(groups) <= 8, f"{who}: one to eight parameter groups")
+    if ranges:
+        prev = 0
+        for g in groups:
+            _req(prev <= g.begin <= g.end <= n and g.begin % 8 == 0,
+                 f"{who} groups: sorted, disjoint ranges of the store that begin on a multiple of 8")
+            prev = g.end
+    return end
+
+
+def _clip_check(who, clip_coef):
+    _req(clip_coef is None or (clip_coef.is_cuda and clip_coef.dtype == F32 and clip_coef.numel() >= 1),
+         f"{who} clip coefficient: a device fp32 scalar")
+
+
 def adamw_bf16(p, g, m, v, groups, clip_coef=None, stochastic_rounding=True, seed=0, begin=0, end=None):
     """fused AdamW(+SR) over elements [begin, end) of the flat bf16 buffers (default: all)."""
     n = p.numel()
-    end = n if end is None else end
     for t in (p, g, m, v):
         _req(t.dtype == BF16 and t.is_contiguous() and t.numel() == n and _aligned(t), "adamw flat bf16 buffers")
-    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0, "adamw range: multiples of 8 within the store")
+    end = _window_checks("adamw", n, begin, end)
     arr = (_lib.AdamwGroup * len(groups))(*groups)
     check(lib().otamd_adamw_bf16_range(_p(p), _p(g), _p(m), _p(v), begin, end, arr, len(groups), _p(clip_coef),
                                        int(stochastic_rounding), seed & 0xFFFFFFFFFFFFFFFF, stream_handle()),
@@ -865,12 +907,11 @@ def adamw_master(p32, g, m32, v32, w, groups, clip_coef=None, begin=0, end=None)
     """fp32-master AdamW over elements [begin, end): fp32 p / m / v, bf16 gradients in, the bf16 working copy w
     rewritten as rne(p) (util/optimizer/adamw_fused.py, master stores)."""
     n = p32.numel()
-    end = n if end is None else end
     for t in (p32, m32, v32):
         _req(t.dtype == F32 and t.is_contiguous() and t.numel() == n and _aligned(t), "adamw master f32 buffers")
     for t in (g, w):
         _req(t.dtype == BF16 and t.is_contiguous() and t.numel() == n and _aligned(t), "adamw master bf16 buffers")
-    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0, "adamw range: multiples of 8 within the store")
+    end = _window_checks("adamw", n, begin, end)
     arr = (_lib.AdamwGroup * len(groups))(*groups)
     check(lib().otamd_adamw_master_range(_p(p32), _p(g), _p(m32), _p(v32), _p(w), begin, end, arr, len(groups),
                                          _p(clip_coef), stream_handle()),
@@ -879,26 +920,18 @@ def adamw_master(p32, g, m32, v32, w, groups, clip_coef=None, begin=0, end=None)
 
 def _factored_step_checks(who, p, g, w, flat_f32, f32, slab_sq, sq_per_slab, scal, scal_per_tensor, tensors_dev,
                           t_range, slabs_dev, s_range, groups) -> int:
-    """the argument checks adafactor_step and came_step share; returns the form (0 bf16 store, 1 fp32 store, 2 fp32
-    master + bf16 working copy w).  flat_f32: further fp32 buffers indexed as the store; f32: fp32 state buffers."""
-    n = p.numel()
-    _req(p.dtype in (BF16, F32) and g.dtype in (BF16, F32), f"{who} flat buffers: bf16 or fp32")
-    if w is not None:
-        form = 2
-        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, f"{who} master: fp32 p, bf16 g and w")
-    else:
-        form = 0 if p.dtype == BF16 else 1
-        _req(g.dtype == p.dtype, f"{who}: gradients in the store's dtype")
-    for t in (p, g) + tuple(flat_f32) + ((w,) if w is not None else ()):
-        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), f"{who} flat buffers")
-    for t in tuple(flat_f32) + tuple(f32) + (scal,):
+    """the argument checks adafactor_step and came_step share beyond the flat-store ones; returns the form (store_form).
+    flat_f32: further fp32 buffers indexed as the store; f32: fp32 state buffers the tables index."""
+    form = store_form(p, g, w, who)
+    _flat_checks(who, p.numel(), (p, g, w), flat_f32)
+    for t in tuple(f32) + (scal,):
         _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and _aligned(t), f"{who} fp32 buffers")
     nt, ns = tensors_dev.numel() // C.sizeof(_lib.AdafactorTensor), slabs_dev.numel() // C.sizeof(_lib.AdafactorSlab)
     _req(slab_sq.is_cuda and slab_sq.dtype == torch.float64 and slab_sq.numel() >= sq_per_slab * ns,
          f"{who} slab_sq f64[{sq_per_slab} * slabs]")
     _req(scal.numel() >= scal_per_tensor * nt, f"{who} scal f32[{scal_per_tensor} * tensors]")
     _req(0 <= t_range[0] <= t_range[1] <= nt and 0 <= s_range[0] <= s_range[1] <= ns, f"{who} table ranges")
-    _req(1 <= len(groups) <= 8, f"{who}: 1..8 parameter groups")
+    _window_checks(who, p.numel(), 0, None, groups)
     return form
 
 
@@ -940,24 +973,6 @@ def came_step(p, g, w, m, state_sq, state_res, scratch_sq, scratch_res, slab_sq,
           "otamd_came_step")
 
 
-def prodigy_form(p, g, w) -> int:
-    """the C-ABI form code of csrc/prodigy.hip: 0 bf16 store, 1 fp32 store, 2 fp32 master p with bf16 gradients and
-    the bf16 working copy w"""
-    if w is not None:
-        _req(p.dtype == F32 and g.dtype == BF16 and w.dtype == BF16, "prodigy master: fp32 p, bf16 g and w")
-        return 2
-    _req(p.dtype in (BF16, F32) and g.dtype == p.dtype, "prodigy: a bf16 or fp32 store with gradients in its dtype")
-    return 0 if p.dtype == BF16 else 1
-
-
-def _prodigy_flat(n, same, f32):
-    for t in same:
-        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "prodigy flat buffers")
-    for t in f32:
-        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == n and _aligned(t),
-             "prodigy fp32 states, indexed as the store")
-
-
 def _prodigy_state(state):
     _req(state.is_cuda and state.dtype == torch.float64 and state.is_contiguous()
          and state.numel() * 8 == C.sizeof(_lib.ProdigyState), "prodigy state block")
@@ -967,9 +982,9 @@ def prodigy_accumulate(p, g, w, p0, m, v, s, chunks_dev, n_chunks, chunk_num, ch
                        capture_p0=False):
     """pass 1 of a fused Prodigy step (csrc/prodigy.hip): the states m (None when beta1 == 0), v, s and the two
     per-chunk fp64 sums over the grad-norm chunk table, whose ranges the caller checked
-    (util/optimizer/prodigy_fused.py).  p / g / w as prodigy_form; state: the device ProdigyState (fp64[8])."""
-    form = prodigy_form(p, g, w)
-    _prodigy_flat(p.numel(), (p, g), (p0, v, s) + ((m,) if m is not None else ()))
+    (util/optimizer/prodigy_fused.py).  p / g / w as store_form; state: the device ProdigyState (fp64[8])."""
+    form = store_form(p, g, w, "prodigy")
+    _flat_checks("prodigy", p.numel(), (p, g), (p0, v, s, m))
     _prodigy_state(state)
     _req(m is not None or hyper.beta1 == 0.0, "prodigy: the first moment is required when beta1 > 0")
     _req(0 <= n_chunks <= chunks_dev.numel() // C.sizeof(_lib.NormChunk), "prodigy chunk table")
@@ -993,8 +1008,8 @@ def prodigy_finalize(chunk_num, chunk_den, n_chunks, state, hyper):
 
 def prodigy_apply(p, g, w, m, v, state, hyper, clip_coef=None, stochastic_rounding=False, seed=0):
     """pass 3: the parameter update over the whole store with the new d the finalize left in `state`"""
-    form = prodigy_form(p, g, w)
-    _prodigy_flat(p.numel(), (p, g) + ((w,) if w is not None else ()), (v,) + ((m,) if m is not None else ()))
+    form = store_form(p, g, w, "prodigy")
+    _flat_checks("prodigy", p.numel(), (p, g, w), (v, m))
     _prodigy_state(state)
     _req(m is not None or hyper.beta1 == 0.0, "prodigy: the first moment is required when beta1 > 0")
     check(lib().otamd_prodigy_apply(_p(p), _p(w), _p(g), form, _p(m), _p(v), p.numel(), _p(state), C.byref(hyper),
@@ -1003,36 +1018,14 @@ def prodigy_apply(p, g, w, m, v, state, hyper, clip_coef=None, stochastic_roundi
           "otamd_prodigy_apply")
 
 
-def _sf_checks(p, w, z, others, f32, groups, begin, end):
-    """the argument checks sf_adamw_step and sf_swap share; returns (form, end).  others: further buffers in p's
-    layout whatever their dtype; f32: fp32 states indexed as the store; groups: SfGroup / SfSwapGroup sorted by begin."""
-    n = p.numel()
-    end = n if end is None else end
-    for t in (p,) + tuple(others) + ((w,) if w is not None else ()):
-        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t),
-             "schedule-free flat buffers")
-    for t in (z,) + tuple(f32):
-        _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and t.numel() == n and _aligned(t),
-             "schedule-free fp32 states, indexed as the store")
-    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0,
-         "schedule-free range: multiples of 8 within the store")
-    _req(1 <= len(groups) <= 8, "schedule-free: one to eight parameter groups")
-    prev = 0
-    for g in groups:
-        _req(prev <= g.begin <= g.end <= n and g.begin % 8 == 0,
-             "schedule-free groups: sorted, disjoint ranges of the store that begin on a multiple of 8")
-        prev = g.end
-    return end
-
-
 def sf_adamw_step(p, g, w, z, v, groups, clip_coef=None, stochastic_rounding=False, seed=0, begin=0, end=None):
     """one fused schedule-free AdamW step (csrc/schedule_free.hip) over elements [begin, end) of the store (default:
-    all).  p / g / w as prodigy_form (bf16 store; fp32 store; fp32 master p with bf16 gradients and the bf16 working
+    all).  p / g / w as store_form (bf16 store; fp32 store; fp32 master p with bf16 gradients and the bf16 working
     copy w); z, v: fp32 states indexed as the store; groups: _lib.SfGroup sorted by begin, scalars from the host."""
-    form = prodigy_form(p, g, w)
-    end = _sf_checks(p, w, z, (g,), (v,), groups, begin, end)
-    _req(clip_coef is None or (clip_coef.is_cuda and clip_coef.dtype == F32 and clip_coef.numel() >= 1),
-         "schedule-free clip coefficient: a device fp32 scalar")
+    form = store_form(p, g, w, "schedule-free")
+    _flat_checks("schedule-free", p.numel(), (p, g, w), (z, v))
+    end = _window_checks("schedule-free", p.numel(), begin, end, groups, ranges=True)
+    _clip_check("schedule-free", clip_coef)
     arr = (_lib.SfGroup * len(groups))(*groups)
     check(lib().otamd_sf_adamw_step(_p(p), _p(w), _p(g), form, _p(z), _p(v), p.numel(), begin, end, arr, len(groups),
                                     _p(clip_coef), int(stochastic_rounding), seed & 0xFFFFFFFFFFFFFFFF,
@@ -1043,13 +1036,9 @@ def sf_adamw_step(p, g, w, z, v, groups, clip_coef=None, stochastic_rounding=Fal
 def sf_swap(p, w, z, groups, begin=0, end=None):
     """p <- p + w_group (z - p) over the groups' ranges inside [begin, end): the eval() / train() switch of the
     schedule-free optimizer.  p / w as above (a bf16 store is rounded to nearest); groups: _lib.SfSwapGroup."""
-    if w is not None:
-        _req(p.dtype == F32 and w.dtype == BF16, "schedule-free master: fp32 p and its bf16 working copy")
-        form = 2
-    else:
-        _req(p.dtype in (BF16, F32), "schedule-free: a bf16 or fp32 store")
-        form = 0 if p.dtype == BF16 else 1
-    end = _sf_checks(p, w, z, (), (), groups, begin, end)
+    form = store_form(p, None, w, "schedule-free")
+    _flat_checks("schedule-free", p.numel(), (p, w), (z,))
+    end = _window_checks("schedule-free", p.numel(), begin, end, groups, ranges=True)
     arr = (_lib.SfSwapGroup * len(groups))(*groups)
     check(lib().otamd_sf_swap(_p(p), _p(w), form, _p(z), p.numel(), begin, end, arr, len(groups), stream_handle()),
           "otamd_sf_swap")
@@ -1064,14 +1053,13 @@ def adamw8bit_check(table_host, n_segs, n, n_absmax, n_f32, n_groups) -> int:
 def adamw8bit_step(p, g, w, code1, code2, absmax1, absmax2, m32, v32, qmap, table, table_host, n_segs, groups,
                    clip_coef=None, stochastic_rounding=False, seed=0):
     """one fused 8-bit AdamW step (csrc/adamw8bit.hip) over every tensor of the segment table.  p / g / w as
-    prodigy_form; code1 / code2: uint8 indexed as the store; absmax1 / absmax2: fp32 per 256-element block; m32 / v32:
+    store_form; code1 / code2: uint8 indexed as the store; absmax1 / absmax2: fp32 per 256-element block; m32 / v32:
     the fp32 moments of the tensors below min_8bit_size; qmap: 512 fp32, the signed then the unsigned codebook.
     table: device bytes of _lib.A8Seg[n_segs]; table_host: the same array as a ctypes object (checked by the library on
     every call); groups: _lib.A8Group indexed by the segments' `group`."""
-    form = prodigy_form(p, g, w)
+    form = store_form(p, g, w, "adamw8bit")
     n = p.numel()
-    for t in (p, g) + ((w,) if w is not None else ()):
-        _req(t.is_cuda and t.is_contiguous() and t.numel() == n and n % 8 == 0 and _aligned(t), "adamw8bit flat buffers")
+    _flat_checks("adamw8bit", n, (p, g, w))
     for t in (code1, code2):
         _req(t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and _aligned(t),
              "adamw8bit codes: uint8, indexed as the store")
@@ -1081,9 +1069,8 @@ def adamw8bit_step(p, g, w, code1, code2, absmax1, absmax2, m32, v32, qmap, tabl
     _req(qmap.numel() == 512, "adamw8bit codebooks: 2 x 256 fp32")
     _req(table.is_cuda and table.dtype == torch.uint8 and table.numel() == n_segs * C.sizeof(_lib.A8Seg) and n_segs >= 1,
          "adamw8bit table")
-    _req(1 <= len(groups) <= 8, "adamw8bit: one to eight parameter groups")
-    _req(clip_coef is None or (clip_coef.is_cuda and clip_coef.dtype == F32 and clip_coef.numel() >= 1),
-         "adamw8bit clip coefficient: a device fp32 scalar")
+    _window_checks("adamw8bit", n, 0, None, groups)
+    _clip_check("adamw8bit", clip_coef)
     arr = (_lib.A8Group * len(groups))(*groups)
     check(lib().otamd_adamw8bit_step(_p(p), _p(w), _p(g), form, _p(code1), _p(code2), _p(absmax1), _p(absmax2),
                                      absmax1.numel(), _p(m32), _p(v32), m32.numel(), _p(qmap), n, _p(table),
@@ -1104,11 +1091,10 @@ def ema_update(ema, p, one_minus_decay: float, begin=0, end=None):
     """ema <- ema + one_minus_decay * (p - ema) over elements [begin, end) of the flat buffers (default: all), with
     the three torch roundings of EMAModuleWrapper.step; one launch (csrc/ema.hip)."""
     n = p.numel()
-    end = n if end is None else end
     form = ema_form(ema, p)
     for t in (ema, p):
         _req(t.is_cuda and t.is_contiguous() and t.numel() == n and _aligned(t), "ema flat buffers")
-    _req(0 <= begin <= end <= n and begin % 8 == 0 and end % 8 == 0, "ema range: multiples of 8 within the store")
+    end = _window_checks("ema", n, begin, end)
     check(lib().otamd_ema_range(_p(ema), _p(p), form, begin, end, float(one_minus_decay), stream_handle()),
           "otamd_ema_range")
 

@@ -345,12 +345,12 @@ class GenericTrainer(TimedActionMixin):
 
     def _attach_norm_overlap(self):
         """eager steps, clip on, a fused flat-store optimizer (AdamW, Adafactor, CAME, Prodigy): clip_grad_norm_'s norm pass runs during backward
-        (util/optimizer/adamw_fused.OverlappedGradNorm) -- in one process as gradient ranges finish, under data
+        (util/optimizer/flat_store.OverlappedGradNorm) -- in one process as gradient ranges finish, under data
         parallel as the reducer's buckets finish their all-reduce (the norm of the global-mean gradients)."""
         import os
 
         from ..module import streams as S
-        from ..util.optimizer.adamw_fused import FlatStoreOptimizer, OverlappedGradNorm
+        from ..util.optimizer.flat_store import FlatStoreOptimizer, OverlappedGradNorm
         opt = getattr(self.model, "optimizer", None)
         if (isinstance(opt, FlatStoreOptimizer) and self.graphs is None and self.config.clip_grad_norm
                 and opt.store.grad.is_cuda and S.enabled() and os.environ.get("OTAMD_NORM_OVERLAP", "1") != "0"

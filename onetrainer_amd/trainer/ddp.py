@@ -25,7 +25,7 @@ on one GPU.  Gradients are left as they are.
 
 Completion: on a GPU every bucket's completion is taken on a post stream -- it waits for the collective, copies an
 fp32-staged bucket back, then runs `reduced_hooks(bucket)` (the clip norm's squared sums of the bucket's chunks,
-util/optimizer/adamw_fused.OverlappedGradNorm), so clip_grad_norm_ after the last bucket only folds per-chunk sums
+util/optimizer/flat_store.OverlappedGradNorm), so clip_grad_norm_ after the last bucket only folds per-chunk sums
 instead of re-reading every gradient (~1.8 ms per SDXL step); `finish()` orders the current stream after it.
 
 Reduction dtype: bf16 in place (default: 2 B/param on the wire, the reference's grad dtype) or,

@@ -43,7 +43,7 @@ import torch
 
 from ... import _lib
 from ... import kernels as K
-from .adamw_fused import FlatStoreOptimizer
+from .flat_store import FlatStoreOptimizer
 
 BLOCK = 256
 
@@ -96,6 +96,8 @@ def group_scalars(g, step: int) -> dict:
 
 
 class FusedAdamW8bit(FlatStoreOptimizer):
+    TUPLE_KEYS = ("betas",)
+
     def __init__(self, store, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  min_8bit_size=4096, stochastic_rounding=True, seed=0):
         if not int(min_8bit_size) >= 1:
@@ -114,7 +116,7 @@ class FusedAdamW8bit(FlatStoreOptimizer):
         segs = []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
-                s = store.slots[self._ptr2name[p.data_ptr()]]
+                s = store.slots[self._name(p)]
                 if s.numel > 0:
                     segs.append((s.offset, s.offset + s.numel, gi, s.name))
         segs.sort()
@@ -134,8 +136,7 @@ class FusedAdamW8bit(FlatStoreOptimizer):
             else:
                 n_f32 += (e - b + 7) // 8 * 8
         self._table_host, self._n_segs = arr, len(segs)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        self._table = raw.to(dev)
+        self._table = self._to_device(arr)
         self.qmap1, self.qmap2 = dynamic_map(True), dynamic_map(False)
         self.zero_code1 = int(np.flatnonzero(self.qmap1 == 0)[0])   # 127; the unsigned map's is 0
         self.zero_code2 = int(np.flatnonzero(self.qmap2 == 0)[0])
@@ -161,19 +162,17 @@ class FusedAdamW8bit(FlatStoreOptimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        clip = self.clip_out if self._pending_clip else None
-        self._pending_clip = False
+        clip = self._take_clip()
         st = self.store
         st.wait_params()
         if self._n_segs == 0:
             return loss
-        p, w = (self.master, st.data) if self.master is not None else (st.data, None)
-        bf16_store = w is None and st.dtype == torch.bfloat16
-        if bf16_store:
-            self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        p, w = self._pw()
+        self._advance_seed()
         K.adamw8bit_step(p, st.grad, w, self.code1, self.code2, self.absmax1, self.absmax2, self.m32, self.v32,
                          self._qmap, self._table, self._table_host, self._n_segs, self._groups_struct(),
-                         clip_coef=clip, stochastic_rounding=self.stochastic_rounding and bf16_store, seed=self.seed)
+                         clip_coef=clip, stochastic_rounding=self.stochastic_rounding and self._bf16_store,
+                         seed=self.seed)
         return loss
 
     def step_parameter(self, p, group, i):
@@ -189,51 +188,27 @@ class FusedAdamW8bit(FlatStoreOptimizer):
         is8, off, nblk = self._seg_of[name]
         if not is8:
             return {"state1": self.m32[off:off + s.numel].view(s.shape), "state2": self.v32[off:off + s.numel].view(s.shape)}
-        sl = slice(s.offset, s.offset + s.numel)
-        return {"state1": self.code1[sl].view(s.shape), "state2": self.code2[sl].view(s.shape),
+        return {"state1": self._flat(self.code1, name), "state2": self._flat(self.code2, name),
                 "absmax1": self.absmax1[off:off + nblk], "absmax2": self.absmax2[off:off + nblk]}
 
-    def state_dict(self):
-        self.store.wait_params()
-        state, groups, idx = {}, [], 0
-        for gi, g in enumerate(self.param_groups):
-            ids = []
-            for p in g["params"]:
-                if self.steps[gi] > 0:   # before the first step there is no state, as for any torch optimizer
-                    views = self._views(self._ptr2name[p.data_ptr()])
-                    d = {"step": torch.tensor(float(self.steps[gi]))}
-                    d.update({k: v.clone() for k, v in views.items()})
-                    if "absmax1" in views:
-                        d["qmap1"], d["qmap2"] = torch.from_numpy(self.qmap1.copy()), torch.from_numpy(self.qmap2.copy())
-                    state[idx] = d
-                ids.append(idx)
-                idx += 1
-            gd = {k: v for k, v in g.items() if k != "params"}
-            gd["params"] = ids
-            groups.append(gd)
-        # the stochastic-rounding stream position, so that a resumed run rounds like an uninterrupted one
-        return {"state": state, "param_groups": groups, "sr_seed": int(self.seed)}
+    def _has_state(self, name, gi):
+        return self.steps[gi] > 0   # before the first step there is no state, as for any torch optimizer
 
-    def load_state_dict(self, sd):
-        self.store.wait_params()
-        if sd.get("sr_seed") is not None:
-            self.seed = int(sd["sr_seed"])
-        for gi, (g, gsd) in enumerate(zip(self.param_groups, sd["param_groups"])):
-            for k, v in gsd.items():
-                if k != "params":
-                    g[k] = tuple(v) if k == "betas" else v
-            check_hyper(g)
-            for p, pid in zip(g["params"], gsd["params"]):
-                st = sd["state"].get(pid)
-                if not st:
-                    continue   # starts fresh: the codes of 0, absmax 0, fp32 zeros
-                name = self._ptr2name[p.data_ptr()]
-                views = self._views(name)
-                if ("absmax1" in views) != ("absmax1" in st):
-                    raise ValueError(f"ADAMW_8BIT state of {name}: saved with another min_8bit_size")
-                for key in ("qmap1", "qmap2"):
-                    if key in st and not np.array_equal(torch.as_tensor(st[key]).cpu().numpy(), getattr(self, key)):
-                        raise ValueError(f"ADAMW_8BIT state of {name}: {key} is not this build's codebook")
-                for k, v in views.items():
-                    v.copy_(torch.as_tensor(st[k]).to(device=v.device, dtype=v.dtype).reshape(v.shape))
-                self.steps[gi] = int(float(st["step"]))
+    def _save_tensor(self, name, gi):
+        d = {"step": torch.tensor(float(self.steps[gi])), **super()._save_tensor(name, gi)}
+        if "absmax1" in d:
+            d["qmap1"], d["qmap2"] = torch.from_numpy(self.qmap1.copy()), torch.from_numpy(self.qmap2.copy())
+        return d
+
+    def _group_loaded(self, g):
+        check_hyper(g)
+
+    def _load_tensor(self, name, gi, st):
+        """bit for bit; a parameter without saved state keeps the codes of 0, absmax 0, fp32 zeros"""
+        if ("absmax1" in self._views(name)) != ("absmax1" in st):
+            raise ValueError(f"ADAMW_8BIT state of {name}: saved with another min_8bit_size")
+        for key in ("qmap1", "qmap2"):
+            if key in st and not np.array_equal(torch.as_tensor(st[key]).cpu().numpy(), getattr(self, key)):
+                raise ValueError(f"ADAMW_8BIT state of {name}: {key} is not this build's codebook")
+        super()._load_tensor(name, gi, st)
+        self.steps[gi] = int(float(st["step"]))

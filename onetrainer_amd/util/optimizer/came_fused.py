@@ -32,7 +32,7 @@ import torch
 
 from ... import _lib
 from ... import kernels as K
-from .factored_store import FactoredStoreOptimizer, _to_device
+from .factored_store import FactoredStoreOptimizer
 
 FOLD_BLOCK = 256   # csrc/came.hip: AF_THREADS rows, or columns, per fold workgroup (a thread each)
 
@@ -105,7 +105,7 @@ class FusedCAME(FactoredStoreOptimizer):
     def _alloc(self, tensors, n_state, n_scratch):
         dev = self.store.device
         fold, self._nf, self._nm, self._fold_ranges = came_fold_table(tensors, self._nt)
-        self._fold = _to_device(fold, dev)
+        self._fold = self._to_device(fold)
         self.exp_avg = torch.zeros(self.store.numel, dtype=torch.float32, device=dev)   # first moment, store layout
         self.state_buf = torch.zeros(n_state, dtype=torch.float32, device=dev)       # row / column / full second moments
         self.res_buf = torch.zeros(n_state, dtype=torch.float32, device=dev)         # row / column instability
@@ -147,7 +147,7 @@ class FusedCAME(FactoredStoreOptimizer):
         """{state key: view of its buffer} of one tensor's moments"""
         s = self.store.slots[name]
         t = self._table[self._tindex[name]]
-        v = {"exp_avg": self.exp_avg[s.offset:s.offset + s.numel].view(s.shape)}
+        v = {"exp_avg": self._flat(self.exp_avg, name)}
         if t.mode == 0:
             v["exp_avg_sq"] = self.state_buf[t.full_off:t.full_off + t.numel].view(s.shape)
             return v

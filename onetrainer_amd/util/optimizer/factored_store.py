@@ -1,16 +1,16 @@
 """What the factored optimizers over a FlatParamStore share (FusedAdafactor, adafactor_fused.py; FusedCAME,
 came_fused.py): the tensor and slab tables that csrc/adafactor_walk.h walks, and the optimizer around them: the
-8-group limit, the step counters and the stochastic-rounding seed, step(), step_parameter(), state_dict() and
-load_state_dict().  A subclass supplies its buffers (_alloc), its group structs (_groups_struct), its launch
-(_launch), the views of one tensor's states (_views), and where it differs: the saved 'RMS' (_rms, _load_rms), the
-group keys that load as tuples (TUPLE_KEYS), further per-tensor table ranges (_ranges_all, _ranges_of) and the step
-counts step_parameter uses (_parameter_steps)."""
+8-group limit, the step counters, step(), step_parameter() and the 'step' / 'RMS' entries of the state dict (the
+walk is flat_store.FlatStoreOptimizer's).  A subclass supplies its buffers (_alloc), its group structs
+(_groups_struct), its launch (_launch), the views of one tensor's states (_views), and where it differs: the saved
+'RMS' (_rms, _load_rms), the group keys that load as tuples (TUPLE_KEYS), further per-tensor table ranges
+(_ranges_all, _ranges_of) and the step counts step_parameter uses (_parameter_steps)."""
 from __future__ import annotations
 
 import torch
 
 from ... import _lib
-from .adamw_fused import FlatStoreOptimizer
+from .flat_store import FlatStoreOptimizer
 
 # csrc/adafactor_walk.h: AF_STAGE floats per LDS stage, column tiles of at most AF_CT, AF_STAGES stages per slab
 AF_STAGE, AF_CT, AF_STAGES = 4096, 4080, 8
@@ -109,10 +109,6 @@ def adafactor_tables(entries, store_numel: int):
     return tensors, slabs, len(T), len(S), max(8, state), max(8, scratch)
 
 
-def _to_device(arr, device):
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-
-
 class FactoredStoreOptimizer(FlatStoreOptimizer):
     TUPLE_KEYS = ("eps",)   # group keys that load_state_dict restores as tuples
 
@@ -127,7 +123,7 @@ class FactoredStoreOptimizer(FlatStoreOptimizer):
         entries = []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
-                s = store.slots[self._ptr2name[p.data_ptr()]]
+                s = store.slots[self._name(p)]
                 entries.append((s.offset, s.shape, gi, s.name))
         entries.sort(key=lambda e: e[0])
         tensors, slabs, self._nt, self._ns, n_state, n_scratch = adafactor_tables([e[:3] for e in entries],
@@ -135,7 +131,7 @@ class FactoredStoreOptimizer(FlatStoreOptimizer):
         self._table = [tensors[i] for i in range(self._nt)]          # host copies (state_dict, step_parameter)
         names = [e[3] for e in entries if store.slots[e[3]].numel > 0]
         self._tindex = {n: i for i, n in enumerate(names)}
-        self._tensors, self._slabs = _to_device(tensors, store.device), _to_device(slabs, store.device)
+        self._tensors, self._slabs = self._to_device(tensors), self._to_device(slabs)
         self._alloc(tensors, n_state, n_scratch)
 
     # --- what a subclass may extend ---------------------------------------------------------------------------------
@@ -161,11 +157,9 @@ class FactoredStoreOptimizer(FlatStoreOptimizer):
 
     # --- the optimizer ------------------------------------------------------------------------------------------------
     def _call(self, steps, ranges, clip):
-        st = self.store
-        p = self.master if self.master is not None else st.data
-        w = st.data if self.master is not None else None
-        sr = self.stochastic_rounding and w is None and st.dtype == torch.bfloat16
-        self._launch(p, st.grad, w, self._groups_struct(steps), ranges, clip, sr)
+        p, w = self._pw()
+        self._launch(p, self.store.grad, w, self._groups_struct(steps), ranges, clip,
+                     self.stochastic_rounding and self._bf16_store)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -173,54 +167,33 @@ class FactoredStoreOptimizer(FlatStoreOptimizer):
         self.store.wait_params()
         for gi in range(len(self.param_groups)):
             self.steps[gi] += 1
-        clip = self.clip_out if self._pending_clip else None
-        self._pending_clip = False
-        if self.master is None and self.store.dtype == torch.bfloat16:
-            self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        clip = self._take_clip()
+        self._advance_seed()
         self._call(self.steps, self._ranges_all(), clip)
         return loss
 
     def step_parameter(self, p, group, i):
         """fused-back-pass API: update one parameter tensor."""
         self.store.wait_params()
-        name = self._ptr2name[p.data_ptr()]
+        name = self._name(p)
         if name in self._tindex:
             self._call(self._parameter_steps(name, group), self._ranges_of(self._tindex[name]), None)
 
-    # --- state in the reference optimizer's layout --------------------------------------------------------------------
+    # --- state in the reference optimizer's layout: every tensor of the table, from the start ------------------------
+    def _has_state(self, name, gi):
+        return name in self._tindex   # an empty tensor has no table entry
+
     def state_dict(self):
         self.store.wait_params()
-        state, groups, idx = {}, [], 0
-        rms = self._rms()
-        for gi, g in enumerate(self.param_groups):
-            ids = []
-            for p in g["params"]:
-                name = self._ptr2name[p.data_ptr()]
-                if name in self._tindex:
-                    d = {"step": self.steps[gi], "RMS": rms[self._tindex[name]].clone()}
-                    d.update({k: v.clone() for k, v in self._views(name).items()})
-                    state[idx] = d
-                ids.append(idx)
-                idx += 1
-            gd = {k: v for k, v in g.items() if k != "params"}
-            gd["params"] = ids
-            groups.append(gd)
-        # the stochastic-rounding stream position, so that a resumed run rounds like an uninterrupted one
-        return {"state": state, "param_groups": groups, "sr_seed": int(self.seed)}
+        self._rms_saved = self._rms()   # one read-back for the whole dict
+        return super().state_dict()
 
-    def load_state_dict(self, sd):
-        self.store.wait_params()
-        if "sr_seed" in sd:
-            self.seed = int(sd["sr_seed"])
-        for gi, (g, gsd) in enumerate(zip(self.param_groups, sd["param_groups"])):
-            for k, v in gsd.items():
-                if k != "params":
-                    g[k] = tuple(v) if k in self.TUPLE_KEYS else v
-            for p, pid in zip(g["params"], gsd["params"]):
-                name = self._ptr2name[p.data_ptr()]
-                st = sd["state"].get(pid)
-                if st and name in self._tindex:
-                    for k, v in self._views(name).items():
-                        v.copy_(st[k].reshape(v.shape))
-                    self._load_rms(self._tindex[name], float(st.get("RMS", 0.0)))
-                    self.steps[gi] = int(float(st["step"]))
+    def _save_tensor(self, name, gi):
+        return {"step": self.steps[gi], "RMS": self._rms_saved[self._tindex[name]].clone(),
+                **super()._save_tensor(name, gi)}
+
+    def _load_tensor(self, name, gi, st):
+        if name in self._tindex:
+            super()._load_tensor(name, gi, st)
+            self._load_rms(self._tindex[name], float(st.get("RMS", 0.0)))
+            self.steps[gi] = int(float(st["step"]))

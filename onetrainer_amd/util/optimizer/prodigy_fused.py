@@ -46,7 +46,7 @@ import torch
 
 from ... import _lib
 from ... import kernels as K
-from .adamw_fused import FlatStoreOptimizer
+from .flat_store import FlatStoreOptimizer
 
 CHUNK = 1 << 16   # elements of a NormChunk at most (FlatStoreOptimizer._init_store)
 HYPER_KEYS = ("betas", "beta3", "eps", "weight_decay", "decouple", "use_bias_correction", "safeguard_warmup", "d0",
@@ -80,6 +80,8 @@ def check_chunks(chunks, n_chunks, numel):
 
 
 class FusedProdigy(FlatStoreOptimizer):
+    TUPLE_KEYS = ("betas",)
+
     def __init__(self, store, param_groups, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0,
                  decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                  growth_rate=float("inf"), stochastic_rounding=False, seed=0):
@@ -179,17 +181,13 @@ class FusedProdigy(FlatStoreOptimizer):
         loss = closure() if closure is not None else None
         self._poll()
         lr = self._common_lr()
-        clip = self.clip_out if self._pending_clip else None
-        self._pending_clip = False
+        clip = self._take_clip()
         if lr == 0.0:   # a complete no-op: no state, no k, no p0
             return loss
         st = self.store
         st.wait_params()
-        p = self.master if self.master is not None else st.data
-        w = st.data if self.master is not None else None
-        bf16_store = w is None and st.dtype == torch.bfloat16
-        if bf16_store:
-            self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        p, w = self._pw()
+        self._advance_seed()
         h = self._hyper(lr)
         K.prodigy_accumulate(p, st.grad, w, self.p0, self.exp_avg, self.exp_avg_sq, self.s, self._chunks,
                              self._n_chunks, self._chunk_num, self._chunk_den, self._state, h, clip_coef=clip,
@@ -197,69 +195,47 @@ class FusedProdigy(FlatStoreOptimizer):
         self._p0_set = True
         K.prodigy_finalize(self._chunk_num, self._chunk_den, self._n_chunks, self._state, h)
         K.prodigy_apply(p, st.grad, w, self.exp_avg, self.exp_avg_sq, self._state, h, clip_coef=clip,
-                        stochastic_rounding=self.stochastic_rounding and bf16_store, seed=self.seed)
+                        stochastic_rounding=self.stochastic_rounding and self._bf16_store, seed=self.seed)
         self._enqueue_d_copy()
         return loss
 
     def step_parameter(self, p, group, i):
         raise NotImplementedError("PRODIGY step_parameter (fused_back_pass): the step needs sums over the whole store")
 
-    # --- state --------------------------------------------------------------------------------------------------------
+    # --- state: nothing before the first step, as for any torch optimizer --------------------------------------------
     def _views(self, name):
-        """{state key: view of its buffer} of one tensor"""
-        s = self.store.slots[name]
-        sl = slice(s.offset, s.offset + s.numel)
-        v = {"s": self.s[sl].view(s.shape), "p0": self.p0[sl].view(s.shape),
-             "exp_avg_sq": self.exp_avg_sq[sl].view(s.shape)}
+        v = {"s": self._flat(self.s, name), "p0": self._flat(self.p0, name),
+             "exp_avg_sq": self._flat(self.exp_avg_sq, name)}
         if self.exp_avg is not None:
-            v["exp_avg"] = self.exp_avg[sl].view(s.shape)
+            v["exp_avg"] = self._flat(self.exp_avg, name)
         return v
+
+    def _has_state(self, name, gi):
+        return self._p0_set
+
+    def _save_tensor(self, name, gi):
+        return {"step": self.param_groups[gi]["k"], **super()._save_tensor(name, gi)}
 
     def state_dict(self):
         self.store.wait_params()
         ds = self.d_state()
         for g in self.param_groups:
             g.update({k: ds[k] for k in STATE_KEYS})
-        state, groups, idx = {}, [], 0
-        for g in self.param_groups:
-            ids = []
-            for p in g["params"]:
-                if self._p0_set:   # before the first step there is no state, as for any torch optimizer
-                    d = {"step": ds["k"]}
-                    d.update({k: v.clone() for k, v in self._views(self._ptr2name[p.data_ptr()]).items()})
-                    state[idx] = d
-                ids.append(idx)
-                idx += 1
-            gd = {k: v for k, v in g.items() if k != "params"}
-            gd["params"] = ids
-            gd["sr_seed"] = int(self.seed)
-            groups.append(gd)
-        # the stochastic-rounding stream position, so that a resumed run rounds like an uninterrupted one
-        return {"state": state, "param_groups": groups, "sr_seed": int(self.seed)}
+        sd = super().state_dict()
+        for gd in sd["param_groups"]:
+            gd["sr_seed"] = sd["sr_seed"]   # the groups carry the seed too
+        return sd
 
-    def load_state_dict(self, sd):
-        self.store.wait_params()
+    def _saved_seed(self, sd):
+        """the top-level seed, else the first group's that has one"""
         seeds = [sd.get("sr_seed")] + [g.get("sr_seed") for g in sd["param_groups"]]
-        for seed in seeds:
-            if seed is not None:
-                self.seed = int(seed)
-                break
-        fresh = []
-        for g, gsd in zip(self.param_groups, sd["param_groups"]):
-            for k, v in gsd.items():
-                if k not in ("params", "sr_seed"):
-                    g[k] = tuple(v) if k == "betas" else v
-            for p, pid in zip(g["params"], gsd["params"]):
-                st = sd["state"].get(pid)
-                name = self._ptr2name[p.data_ptr()]
-                if st:
-                    for k, v in self._views(name).items():
-                        src = torch.as_tensor(st[k]).to(device=v.device, dtype=v.dtype)
-                        # a scalar p0 stands for a constant tensor (tensor(0) for an all-zero parameter)
-                        v.copy_(src.expand(v.shape) if src.numel() == 1 else src.reshape(v.shape))
-                    self._p0_set = True
-                else:
-                    fresh.append(name)
+        return next((seed for seed in seeds if seed is not None), None)
+
+    def _load_tensor(self, name, gi, st):
+        super()._load_tensor(name, gi, st)
+        self._p0_set = True
+
+    def _loaded(self, fresh):
         if self._p0_set:   # a tensor without saved state starts here: its p0 is its current value
             for name in fresh:
                 self._views(name)["p0"].copy_(self.store.value(name))

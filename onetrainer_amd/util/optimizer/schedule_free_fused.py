@@ -37,7 +37,7 @@ import torch
 
 from ... import _lib
 from ... import kernels as K
-from .adamw_fused import FlatStoreOptimizer
+from .flat_store import FlatStoreOptimizer
 
 GROUP_KEYS = ("k", "train_mode", "weight_sum", "lr_max", "scheduled_lr", "warmup_steps", "r", "weight_lr_power", "betas",
               "eps", "weight_decay", "lr", "foreach")
@@ -78,6 +78,8 @@ def group_scalars(g) -> dict:
 
 
 class FusedScheduleFreeAdamW(FlatStoreOptimizer):
+    TUPLE_KEYS = ("betas",)
+
     def __init__(self, store, param_groups, lr=0.0025, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, warmup_steps=0,
                  r=0.0, weight_lr_power=2.0, foreach=False, stochastic_rounding=True, seed=0):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, r=r, k=0, warmup_steps=warmup_steps, train_mode=False,
@@ -94,14 +96,7 @@ class FusedScheduleFreeAdamW(FlatStoreOptimizer):
         self._z_set = False    # z = y is taken by the first step that runs
         self._y_saved = None   # eval(): the bits of y (the master, or the store data), for train()
 
-    # --- the store forms ----------------------------------------------------------------------------------------------
-    def _pw(self):
-        """(the buffer that holds the trained values, the bf16 working copy of a master store or None)"""
-        st = self.store
-        if self.master is not None:
-            return self.master, st.data
-        return st.data, None
-
+    # --- the two modes' flag ------------------------------------------------------------------------------------------
     @property
     def train_mode(self) -> bool:
         return bool(self.param_groups[0]["train_mode"])
@@ -133,16 +128,13 @@ class FusedScheduleFreeAdamW(FlatStoreOptimizer):
             raise RuntimeError("Optimizer was not in train mode when step is called. Please insert .train() and "
                                ".eval() calls on the optimizer. See documentation for details.")
         loss = closure() if closure is not None else None
-        clip = self.clip_out if self._pending_clip else None
-        self._pending_clip = False
+        clip = self._take_clip()
         st = self.store
         st.wait_params()
         p, w = self._pw()
-        bf16_store = w is None and st.dtype == torch.bfloat16
-        if bf16_store:
-            self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
+        self._advance_seed()
         K.sf_adamw_step(p, st.grad, w, self.z, self.exp_avg_sq, self._groups_struct(), clip_coef=clip,
-                        stochastic_rounding=self.stochastic_rounding and bf16_store, seed=self.seed)
+                        stochastic_rounding=self.stochastic_rounding and self._bf16_store, seed=self.seed)
         self._z_set = True
         return loss
 
@@ -190,50 +182,23 @@ class FusedScheduleFreeAdamW(FlatStoreOptimizer):
         self._y_saved = None
         self._set_mode(True)
 
-    # --- state --------------------------------------------------------------------------------------------------------
+    # --- state: nothing before the first step, as for any torch optimizer --------------------------------------------
     def _views(self, name):
-        s = self.store.slots[name]
-        sl = slice(s.offset, s.offset + s.numel)
-        return {"z": self.z[sl].view(s.shape), "exp_avg_sq": self.exp_avg_sq[sl].view(s.shape)}
+        return {"z": self._flat(self.z, name), "exp_avg_sq": self._flat(self.exp_avg_sq, name)}
 
-    def state_dict(self):
-        self.store.wait_params()
-        state, groups, idx = {}, [], 0
-        for g in self.param_groups:
-            ids = []
-            for p in g["params"]:
-                if self._z_set:   # before the first step there is no state, as for any torch optimizer
-                    state[idx] = {k: v.clone() for k, v in self._views(self._ptr2name[p.data_ptr()]).items()}
-                ids.append(idx)
-                idx += 1
-            gd = {k: v for k, v in g.items() if k != "params"}
-            gd["params"] = ids
-            groups.append(gd)
-        # the stochastic-rounding stream position, so that a resumed run rounds like an uninterrupted one
-        return {"state": state, "param_groups": groups, "sr_seed": int(self.seed)}
+    def _has_state(self, name, gi):
+        return self._z_set
 
-    def load_state_dict(self, sd):
-        self.store.wait_params()
-        if sd.get("sr_seed") is not None:
-            self.seed = int(sd["sr_seed"])
+    def _group_loaded(self, g):
+        check_hyper(g)
+
+    def _load_tensor(self, name, gi, st):
+        super()._load_tensor(name, gi, st)
+        self._z_set = True
+
+    def _loaded(self, fresh):
         self._y_saved = None   # the store now holds what the state says, not what eval() of this object left
-        fresh = []
-        for g, gsd in zip(self.param_groups, sd["param_groups"]):
-            for k, v in gsd.items():
-                if k not in ("params", "sr_seed"):
-                    g[k] = tuple(v) if k == "betas" else v
-            check_hyper(g)
-            for p, pid in zip(g["params"], gsd["params"]):
-                st = sd["state"].get(pid)
-                name = self._ptr2name[p.data_ptr()]
-                if st:
-                    for k, v in self._views(name).items():
-                        v.copy_(torch.as_tensor(st[k]).to(device=v.device, dtype=v.dtype).reshape(v.shape))
-                    self._z_set = True
-                else:
-                    fresh.append(name)
         if self._z_set:   # a tensor without saved state starts here: x = y = z is its current value
             for name in fresh:
                 self._views(name)["z"].copy_(self.store.value(name))
-        mode = self.train_mode   # one mode for the whole store
-        self._set_mode(mode)
+        self._set_mode(self.train_mode)   # one mode for the whole store

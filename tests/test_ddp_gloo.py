@@ -113,7 +113,7 @@ def test_bucket_allreduce_grad_accumulation_gloo_world2(reduce_fp32):
 
 
 def _worker_norm(rank, world, port, q):
-    """the clip norm under data parallel (util/optimizer/adamw_fused.OverlappedGradNorm(reducer=...)): its ranges are
+    """the clip norm under data parallel (util/optimizer/flat_store.OverlappedGradNorm(reducer=...)): its ranges are
     the reducer's buckets and each is summed from the reducer's completion hook -- every norm chunk exactly once per
     update step, after its bucket holds the global sum, never on a GA micro-step (CPU: the hooks run in finish(); on
     the GPU on the reducer's post stream, tests/test_dp_gpu.py)"""
@@ -121,7 +121,8 @@ def _worker_norm(rank, world, port, q):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from onetrainer_amd.util.optimizer.adamw_fused import FusedAdamW, OverlappedGradNorm
+        from onetrainer_amd.util.optimizer.adamw_fused import FusedAdamW
+        from onetrainer_amd.util.optimizer.flat_store import OverlappedGradNorm
         specs = SPECS + [("big", (70000,), "g")]   # one tensor of two norm chunks (64 K elements each)
         st = FlatParamStore(specs, torch.bfloat16, torch.device("cpu"))
         red = GradBucketReducer(st, bucket_bytes=2048)

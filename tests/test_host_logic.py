@@ -195,7 +195,7 @@ def test_overlapped_norm_buckets_skip_empty_tensors():
     bucket's range back to chunk 0 (every earlier tensor's chunks would be summed twice into the norm)."""
     from types import SimpleNamespace
 
-    from onetrainer_amd.util.optimizer.adamw_fused import OverlappedGradNorm
+    from onetrainer_amd.util.optimizer.flat_store import OverlappedGradNorm
     numels = {"a": 70000, "b": 0, "c": 1000, "d": 0, "e": 5}
     order = list(numels)
     chunk_tensor = []

@@ -255,7 +255,7 @@ def test_grad_norm_overlap_with_untouched_tensors(dev):
     """OverlappedGradNorm when a step's backward leaves some tensors without a gradient: their buckets are summed in
     finish() after finish_backward zeroed them, so the chunk slots of the previous step (poisoned here) never reach
     the clip coefficient, which equals the end-of-step pass over the same gradients."""
-    from onetrainer_amd.util.optimizer.adamw_fused import OverlappedGradNorm
+    from onetrainer_amd.util.optimizer.flat_store import OverlappedGradNorm
     shapes = [(f"t{i}", (300 + 37 * i, 500)) for i in range(12)]
     st = FlatParamStore([(n, s, "g") for n, s in shapes], torch.bfloat16, dev)
     opt = FusedAdamW(st, [{"params": [st.params[n] for n, _ in shapes]}], lr=1e-3)

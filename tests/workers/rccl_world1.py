@@ -50,7 +50,7 @@ def main():
             tr.reducer = GradBucketReducer(model.train_store, bucket_bytes=1 << 20, reduce_fp32=reducer_kind == "fp32")
             nb = len(tr.reducer.buckets)
             if norm_overlap:   # the clip norm's sums per bucket on the reducer's post stream, after each RCCL reduce
-                from onetrainer_amd.util.optimizer.adamw_fused import OverlappedGradNorm
+                from onetrainer_amd.util.optimizer.flat_store import OverlappedGradNorm
                 model.optimizer.norm_overlap = OverlappedGradNorm(model.optimizer, reducer=tr.reducer)
         batch = synthetic_sdxl_batch(2, 128, 128, dev, seed=1, te1_dim=48, te2_dim=48, pooled_dim=64)
         for _ in range(2):
