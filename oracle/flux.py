@@ -69,7 +69,7 @@ def apply_rotary_emb(x, cos, sin):
     """x [B, H, S, D]; interleaved real / imaginary pairs (use_real_unbind_dim=-1)."""
     xr, xi = x.reshape(*x.shape[:-1], -1, 2).unbind(-1)
     rot = torch.stack([-xi, xr], dim=-1).flatten(3)
-    return x * cos[None, None] + rot * sin[None, None]
+    return (x * cos[None, None] + rot * sin[None, None]).to(x.dtype)   # fp32 tables: bf16 rotates in fp32, as diffusers
 
 
 class RMSNorm(nn.Module):
@@ -102,9 +102,10 @@ class CombinedTimestepGuidanceTextProjEmbeddings(nn.Module):
         self.guidance = guidance
 
     def forward(self, timestep, guidance, pooled):
-        emb = self.timestep_embedder(timestep_embedding(timestep, 256))
+        dt = pooled.dtype   # the sinusoids enter in the network's dtype (diffusers: time_proj(...).to(dtype))
+        emb = self.timestep_embedder(timestep_embedding(timestep, 256).to(dt))
         if self.guidance:
-            emb = emb + self.guidance_embedder(timestep_embedding(guidance, 256))
+            emb = emb + self.guidance_embedder(timestep_embedding(guidance, 256).to(dt))
         return emb + self.text_embedder(pooled)
 
 

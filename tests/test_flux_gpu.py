@@ -1,7 +1,10 @@
 """FLUX.1: HIP kernels vs plain PyTorch fp32 references, and the
 HIP FluxTransformer2DModel (bf16, rows t*B + b) vs the oracle restatement (fp32 CPU) -- forward, every
 parameter / LoRA-adapter gradient, and the LoRA train step.  Tolerances: bf16 activations with fp32
-accumulation vs fp32: forward rel err < 3e-2, gradient cosine >= 0.99 (parity unpinned: diffusers absent)."""
+accumulation vs fp32: forward rel err < 3e-2, gradient cosine >= 0.99 (parity unpinned: diffusers absent); every
+gradient also against the float64 oracle per tensor: scale and relative L2 error (_grad_parity.py)."""
+import copy
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -10,6 +13,8 @@ from onetrainer_amd import kernels as K
 from onetrainer_amd.module import flux as FX
 from oracle import flux as OF
 from oracle.lora import OracleLoRA
+
+import _grad_parity as G
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -147,10 +152,12 @@ def test_flux_transformer_matches_oracle(dev, lora):
     om.load_state_dict({k: v.float().cpu() for k, v in m.state_dict().items()})
     B, h, w, L = 2, 16, 12, 7
     lat, packed, t, guid, pooled, ehs = _inputs(cfg, B, h, w, L, dev)
-    lw = ol = None
+    lw = ol = ol64 = None
     if lora:
         from onetrainer_amd.module.lora import LoRAWrapper
         om.requires_grad_(False)
+    om64 = copy.deepcopy(om).double()
+    if lora:
         lw = LoRAWrapper(m, rank=8, alpha=4.0, prefix="lora_transformer", seed=0)
         m.lora = lw
         ol = OracleLoRA(om, 8, 4.0, prefix="lora_transformer")
@@ -158,6 +165,10 @@ def test_flux_transformer_matches_oracle(dev, lora):
         lw.load_state_dict({k: (torch.randn(v.shape, generator=g) * 0.05 if not k.endswith(".alpha") else v)
                             for k, v in lw.state_dict().items()})
         ol.load_state_dict({k: v for k, v in lw.state_dict().items() if not k.endswith(".alpha")})
+        ol64 = OracleLoRA(om64, 8, 4.0, prefix="lora_transformer")
+        ol64.load_state_dict({k: v for k, v in lw.state_dict().items() if not k.endswith(".alpha")})
+        for p in ol64.params.values():
+            p.data = p.data.double()
     tok = packed.bfloat16().transpose(0, 1).reshape(-1, cfg.in_channels).to(dev)   # rows t*B + b
     out = m(tok, t.to(dev), guid.to(dev), pooled.to(dev).bfloat16(), ehs.to(dev).bfloat16(), h, w)
     ref = om(packed.bfloat16().float(), t, guid, pooled.bfloat16().float(), ehs.bfloat16().float(),
@@ -185,6 +196,12 @@ def test_flux_transformer_matches_oracle(dev, lora):
     worst.sort()
     print("worst grad cosines:", worst[:5])
     assert worst[0][0] > 0.99, worst[:5]
+    # the same weights, inputs and upstream gradient in float64: the scale and the size of the error, per tensor
+    r64 = om64(packed.bfloat16().double(), t, guid, pooled.bfloat16().double(), ehs.bfloat16().double(),
+               torch.zeros(L, 3), OF.prepare_latent_image_ids(h, w))
+    (r64.transpose(0, 1).reshape(-1, cfg.in_channels) * wgt.double()).sum().backward()
+    p64 = ol64.params if lora else dict(om64.named_parameters())
+    G.check({k: gs[k].float().cpu() for k in p64}, {k: p.grad for k, p in p64.items()}, f"flux lora={lora}")
 
 
 def test_flux_lora_train_steps(dev):

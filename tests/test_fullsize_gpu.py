@@ -34,6 +34,8 @@ from oracle import diffusion as OD
 from oracle import flux as OF
 from oracle import unet as OU
 
+import _grad_parity as G
+
 pytestmark = pytest.mark.gpu
 
 
@@ -93,6 +95,10 @@ def test_full_unet_matches_oracle(dev, name, res):
     gh = m.state_dict(grads=True)
     cos = sorted((_cos(gh[n].float().cpu(), p.grad), n) for n, p in om.named_parameters())
     print("worst grad cosines:", cos[:4])
+    # scale and relative error against the fp32 oracle, printed only: no bf16 CPU oracle has been measured at full
+    # width, so the bounds of _grad_parity.py are not asserted here
+    wr = G.worst({n: gh[n].float().cpu() for n, p in om.named_parameters() if p.grad is not None}, {n: p.grad for n, p in om.named_parameters() if p.grad is not None})
+    print("worst |s-1|", wr["s"], "worst rel", wr["rel"])
     assert cos[0][0] > 0.98, cos[:4]
     assert sum(c for c, _ in cos) / len(cos) > 0.999
     del m, om
@@ -147,6 +153,10 @@ def test_full_width_sdxl_lora_r32_matches_oracle(dev):
     gs = lw.state_dict(grads=True)
     cos = sorted((_cos(gs[k].float().cpu().reshape(p.shape), p.grad), k) for k, p in ol.params.items())
     print(f"{len(cos)} adapter tensors; worst grad cosines:", cos[:4])
+    # scale and relative error against the fp32 oracle, printed only: no bf16 CPU oracle has been measured at full
+    # width, so the bounds of _grad_parity.py are not asserted here
+    wr = G.worst({k: gs[k].float().cpu() for k in ol.params}, {k: p.grad for k, p in ol.params.items()})
+    print("worst |s-1|", wr["s"], "worst rel", wr["rel"])
     assert len(cos) > 1500
     assert cos[0][0] > 0.98, cos[:4]
     assert sum(c for c, _ in cos) / len(cos) > 0.999
@@ -192,6 +202,10 @@ def test_full_width_flux_blocks_768_match_oracle(dev):
     gh = m.state_dict(grads=True)
     cos = sorted((_cos(gh[n].float().cpu(), p.grad), n) for n, p in om.named_parameters() if p.grad is not None)
     print("worst grad cosines:", cos[:4])
+    # scale and relative error against the fp32 oracle, printed only: no bf16 CPU oracle has been measured at full
+    # width, so the bounds of _grad_parity.py are not asserted here
+    wr = G.worst({n: gh[n].float().cpu() for n, p in om.named_parameters() if p.grad is not None}, {n: p.grad for n, p in om.named_parameters() if p.grad is not None})
+    print("worst |s-1|", wr["s"], "worst rel", wr["rel"])
     assert cos[0][0] > 0.98, cos[:4]
     del m, om
     _free()
@@ -251,6 +265,10 @@ def test_full_width_flux_lora_blocks_768_match_oracle(dev):
     assert set(gs) >= set(ol.params), sorted(set(ol.params) - set(gs))[:5]
     cos = sorted((_cos(gs[k].float().cpu().reshape(p.shape), p.grad), k) for k, p in ol.params.items())
     print(f"{len(cos)} adapter tensors; worst grad cosines:", cos[:4])
+    # scale and relative error against the fp32 oracle, printed only: no bf16 CPU oracle has been measured at full
+    # width, so the bounds of _grad_parity.py are not asserted here
+    wr = G.worst({k: gs[k].float().cpu() for k in ol.params}, {k: p.grad for k, p in ol.params.items()})
+    print("worst |s-1|", wr["s"], "worst rel", wr["rel"])
     assert cos[0][0] > 0.98, cos[:4]
     assert sum(c for c, _ in cos) / len(cos) > 0.999
     del m, om, lw, ol

@@ -1,5 +1,8 @@
 """LoRA on the GPU: the fused second-K-segment GEMMs vs fp32 torch, and a frozen-base LoRA UNet
-forward/backward vs the oracle UNet with the reference LoRA hooks (oracle/lora.py)."""
+forward/backward vs the oracle UNet with the reference LoRA hooks (oracle/lora.py); the adapter gradients also against
+the float64 oracle per tensor: scale and relative L2 error (_grad_parity.py)."""
+import copy
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -9,6 +12,8 @@ from onetrainer_amd.module import unet as U
 from onetrainer_amd.module.lora import LoRAUNetWrapper
 from oracle import unet as OU
 from oracle.lora import OracleLoRA
+
+import _grad_parity as G
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -72,14 +77,18 @@ def test_lora_unet_matches_oracle(dev):
     om = OU.UNet2DConditionModel(OU.UNetConfig(**{k: getattr(cfg, k) for k in OU.UNetConfig.__dataclass_fields__}))
     om.load_state_dict({k: v.float().cpu() for k, v in m.state_dict().items()})
     om.requires_grad_(False)
+    om64 = copy.deepcopy(om).double()
     lw = LoRAUNetWrapper(m, rank=8, alpha=4.0, seed=0)
     m.lora = lw
-    ol = OracleLoRA(om, 8, 4.0)
+    ol, ol64 = OracleLoRA(om, 8, 4.0), OracleLoRA(om64, 8, 4.0)
     g = torch.Generator().manual_seed(3)
     sd = {k: (torch.randn(v.shape, generator=g) * 0.1 if not k.endswith(".alpha") else v)
           for k, v in lw.state_dict().items()}
     lw.load_state_dict(sd)
     ol.load_state_dict({k: v for k, v in lw.state_dict().items() if not k.endswith(".alpha")})
+    ol64.load_state_dict({k: v for k, v in lw.state_dict().items() if not k.endswith(".alpha")})
+    for p in ol64.params.values():
+        p.data = p.data.double()
     B, H, W = 2, 16, 16
     x = torch.randn(B, 4, H, W)
     t = torch.tensor([10, 700], dtype=torch.int32)
@@ -107,6 +116,10 @@ def test_lora_unet_matches_oracle(dev):
     print("worst LoRA grad cosines:", worst[:5])
     assert worst[0][0] > 0.99, worst[:5]
     assert m.store.grad is None     # frozen base: no base gradient buffer at all
+    # the same weights, inputs and upstream gradient in float64: the scale and the size of the error, per tensor
+    r64 = om64(x.bfloat16().double(), t, ehs.bfloat16().double(), te.bfloat16().double(), tid)
+    (r64.permute(0, 2, 3, 1) * wgt.double()).sum().backward()
+    G.check({k: gs[k].float().cpu() for k in ol64.params}, {k: p.grad for k, p in ol64.params.items()}, "lora unet")
 
 
 def test_lora_train_steps(dev):

@@ -1,7 +1,11 @@
-"""Whole-network parity: HIP UNet (bf16, NHWC) vs the oracle UNet (fp32, CPU), same weights."""
+"""Whole-network parity: HIP UNet (bf16, NHWC) vs the oracle UNet (fp32, CPU), same weights; every parameter
+gradient also against the float64 oracle per tensor: scale and relative L2 error (_grad_parity.py)."""
+import copy
+
 import pytest
 import torch
 
+import _grad_parity as G
 from onetrainer_amd.module import unet as U
 from oracle import unet as OU
 
@@ -38,6 +42,7 @@ def test_unet_forward_backward_matches_oracle(dev, cfgname):
     out = m(xin, t.to(dev), ehs.to(dev).bfloat16(), None if te is None else te.to(dev).bfloat16(), dv(tid))
     # oracle sees the same bf16-rounded inputs
     ref = om(x.bfloat16().float(), t, ehs.bfloat16().float(), None if te is None else te.bfloat16().float(), tid)
+    om64 = copy.deepcopy(om).double()
     o4 = out[..., :4].float().cpu()
     r4 = ref.permute(0, 2, 3, 1)
     err = (o4 - r4.detach()).abs().max() / r4.detach().abs().max()
@@ -59,3 +64,7 @@ def test_unet_forward_backward_matches_oracle(dev, cfgname):
         assert c > 0.995, f"{name}: cosine {c}"
     worst.sort()
     print("worst grad cosines:", worst[:5])
+    # the same weights, inputs and upstream gradient in float64: the scale and the size of the error, per tensor
+    r64 = om64(x.bfloat16().double(), t, ehs.bfloat16().double(), None if te is None else te.bfloat16().double(), tid)
+    (r64.permute(0, 2, 3, 1) * w.double()).sum().backward()
+    G.check({k: v.float().cpu() for k, v in g.items()}, {k: p.grad for k, p in om64.named_parameters()}, cfgname)
