@@ -458,6 +458,23 @@ int otamd_dora_project(const void* table_dev, const void* table_host, int n, int
 int otamd_dora_entry_size(void);
 int otamd_dora_max_rank(void);
 
+/* replaces: the crop of mgds ScaleCropImage and RandomFlip / RandomRotate / RandomBrightness / RandomContrast /
+   RandomSaturation / RandomHue between it and EncodeVAE (modules/dataLoader/mixin/DataLoaderText2ImageMixin.py:
+   186-212), for every (sample, variation) of an encode batch in one call.
+   table: {long long src_off, out_off; int C, Hs, Ws, y0, x0, H, W, flip; float cos_a, sin_a, brightness, contrast,
+   saturation, hue} per output, the same array on the device and on the host; the host copy is checked against
+   src_numel / out_numel (elements) before anything is launched.  src: flat fp32 planes [C][Hs][Ws] in [0, 1];
+   out: fp32, entry i's [C][H][W] at out_off; every entry's H, W are the call's.  C = 3, or 1 (a mask: no colour
+   stage).  Order: crop at (y0, x0), flip, rotate (bilinear about the crop's centre, taps outside the crop 0, positive
+   angle counter-clockwise), clamp(x b), clamp(c x + (1 - c) m) with m the image's mean of 0.2989 R + 0.587 G +
+   0.114 B, clamp(s x + (1 - s) gray), hue shift in turns.  A neutral stage (no rotation, 1, 1, 1, 0) is not run: a
+   crop / flip entry is a bit-exact copy.  The mean is summed in a fixed order without atomics (ws: _ws_floats(n, H,
+   W) floats of partial sums); two runs give the same bits.  src and out 16-byte aligned, n <= 65535. */
+int otamd_image_augment(const void* table_dev, const void* table_host, int n, int H, int W, const float* src,
+    long long src_numel, float* out, long long out_numel, float* ws, long long ws_floats, hipStream_t s);
+long long otamd_image_augment_ws_floats(int n, int H, int W);
+int otamd_aug_entry_size(void);
+
 /* replaces: diffusers get_timestep_embedding (UNet time_proj / add_time_proj) */
 int otamd_timestep_embedding(const float* t, int n, int dim, void* out, long long ldo, hipStream_t s);
 

@@ -122,6 +122,13 @@ class DoraEntry(C.Structure):
                 ("rblk0", C.c_int), ("s", C.c_float), ("pad", C.c_int)]
 
 
+class AugEntry(C.Structure):
+    _fields_ = [("src_off", C.c_longlong), ("out_off", C.c_longlong), ("C", C.c_int), ("Hs", C.c_int),
+                ("Ws", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("H", C.c_int), ("W", C.c_int), ("flip", C.c_int),
+                ("cos_a", C.c_float), ("sin_a", C.c_float), ("brightness", C.c_float), ("contrast", C.c_float),
+                ("saturation", C.c_float), ("hue", C.c_float)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
                 ("dout", C.c_void_p), ("delta", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p),
@@ -253,6 +260,10 @@ SIGNATURES: dict[str, list] = {
     "otamd_dora_project": [VP, VP, I, I, I, I, VP, LL, VP, VP, LL, VP, LL, VP, LL, I, VP],
     "otamd_dora_entry_size": [],
     "otamd_dora_max_rank": [],
+    # augment.hip
+    "otamd_image_augment": [VP, VP, I, I, I, VP, LL, VP, LL, VP, LL, VP],
+    "otamd_image_augment_ws_floats": [I, I, I],
+    "otamd_aug_entry_size": [],
     "otamd_timestep_embedding": [VP, I, I, VP, LL, VP],
     "otamd_add": [VP, VP, VP, LL, VP],
     "otamd_dp_emulate": [VP, LL, VP, LL, LL, I, LL, VP],
@@ -351,3 +362,4 @@ def check_layouts():
     assert L.otamd_adamw8bit_seg_size() == C.sizeof(A8Seg)
     assert L.otamd_adamw8bit_group_size() == C.sizeof(A8Group)
     assert L.otamd_dora_entry_size() == C.sizeof(DoraEntry)
+    assert L.otamd_aug_entry_size() == C.sizeof(AugEntry)

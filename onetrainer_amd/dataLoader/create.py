@@ -13,6 +13,9 @@ trainer, on this build's latent cache (dataLoader/latent_cache.py).
     85-86; all ones when the file is missing), cached as latent_mask and required from the cache.  The
     per-concept mask augmentations (RandomCircularMaskShrink / RandomMaskRotateCrop, :122-135) are refused;
     unmasked_probability only acts on mask-input (inpainting) model types (:287-288), which are not loaded.
+  * every training row carries its concept's image dict, seed, index within the concept, image_variations and
+    loss_weight (concept_extras): the writer augments on the device and caches the variations (dataLoader/augment.py,
+    csrc/augment.hip); the validation cache gets no augmentation and one variation.
 mgds itself is not in this image: enumeration and captions follow the reference's
 ConceptConfig fields; the bucket list is dataLoader/aspect_bucketing.py (parity unpinned).
 """
@@ -199,6 +202,17 @@ def _enumerate(cfg, concepts: list) -> list[tuple]:
     return out
 
 
+def concept_extras(concept: dict, index: int) -> dict:
+    """what a cached row takes from its concept beside the image and the caption: the augmentation switches
+    (concept.image), the seed and the image's index within the concept that key the draws, image_variations, and
+    loss_weight (ConceptConfig.py:131-138, 189-197).  Absent keys are off / 1 / 1."""
+    from . import augment as A
+    lw = concept.get("loss_weight")
+    return {"augment": {"image": dict(concept.get("image") or {}), "seed": int(concept.get("seed", 0) or 0),
+                        "index": int(index), "variations": A.variations(concept)},
+            "loss_weight": 1.0 if lw is None else float(lw)}
+
+
 def _tokenizers(cfg):
     from transformers import CLIPTokenizer
     base = cfg.base_model_name
@@ -220,13 +234,19 @@ def build_cache(config, model, device, rank: int = 0, validation: bool = False) 
     from ..module import text_encoder as TE
     cfg = plain(config)
     fam = _family(cfg.model_type)
-    concept_of = None
-    if validation:
+    concept_of = extras = None
+    if validation:   # no augmentation, one variation: held-out losses stay comparable
         held_out = enumerate_validation_samples(cfg)
         samples = [v["sample"] for v in held_out]
         concept_of = [v["concept_index"] for v in held_out]
     else:
-        samples = enumerate_samples(cfg)
+        concepts = _concepts(cfg)
+        listed = _enumerate(cfg, concepts)
+        samples = [s for s, _ in listed]
+        extras, seen = [], {}
+        for _, ci in listed:   # the image's index within its concept keys its augmentation draws
+            extras.append(concept_extras(concepts[ci], seen.get(ci, 0)))
+            seen[ci] = seen.get(ci, 0) + 1
     if not samples:
         raise FileNotFoundError(f"no {'validation' if validation else 'training'} images found in the configured "
                                 "concepts")
@@ -253,6 +273,8 @@ def build_cache(config, model, device, rank: int = 0, validation: bool = False) 
     # folder larger than the open-file limit caches
     if validation:
         rows = ({**r, "concept_index": ci} for r, ci in zip(rows, concept_of))
+    else:
+        rows = ({**r, **x} for r, x in zip(rows, extras))
     writer = LatentCacheWriter(lambda im: model.vae_encoder.encode(im),
                                validation_cache_dir(cfg) if validation else cfg.cache_dir, default_bucketing(cfg),
                                device, rank=rank, text_fn=text_fn,

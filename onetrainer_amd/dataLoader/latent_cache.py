@@ -6,17 +6,28 @@ Replaces what the reference's mgds pipeline does before and around the steps
   SampleVAEDistribution(mean) -> DiskCache -> AspectBatchSorting -> OutputPipelineModule.
 The mgds on-disk cache format is not pinned (mgds is not in this image); this build's format:
   <cache_dir>/index.json            {"version": 1, "samples": [{"file", "crop_resolution"}, ...]}
+                                    a sample with image variations adds "variations": [file of variation 1, 2, ...],
+                                    a concept loss weight other than 1 adds "loss_weight"
                                     the held-out set's cache (<cache_dir>/validation) adds "concept_index" to every
                                     entry and "concepts": [{"name", "path", "seed"}, ...] to the index
   <cache_dir>/<i:08d>.safetensors   latent_image [h, w, C] fp32 NHWC (VAE latent_dist.mean, unscaled; C = 4, FLUX.1 16),
                                     original_resolution / crop_offset / crop_resolution int64 [2],
                                     optional cached text states (text_encoder_*_hidden_state, pooled),
                                     optional latent_mask [1, h, w] fp32 in [0, 1] (masked training).
+  <cache_dir>/<i:08d>.v<v>.safetensors   variation v >= 1 of sample i (concept.image_variations): only what differs
+                                    from variation 0 -- latent_image, crop_offset, latent_mask.  Text states are
+                                    cached once per image, in the sample's own file.
 Images are scaled / cropped on the host (data-loader work, as in mgds' worker threads), encoded on
 the GPU by the HIP VAE in same-resolution batches, and written by rank 0 only.
 A sample's mask (masked training: <stem>-masklabel.png, one channel) takes the scale and crop of its image, then
 the downscale to the latent grid (0.125x for the 8x VAEs, StableDiffusionXLBaseDataLoader.py:70) with the same
 antialiased bilinear resize and a clamp to [0, 1].  mgds' exact ScaleImage filter is unpinned (mgds is not in this image).
+A sample of a concept with image_variations > 1 or any image augmentation switched on (dataLoader/augment.py) is
+scaled on the host, uploaded once uncropped, and cropped / flipped / rotated / colour-shifted into all its variations
+on the device (csrc/augment.hip) in front of the encoder; its mask rides through the same launch with the same crop,
+flip and rotation.  Every other sample takes the host crop, and its files and index entry are what they always were.
+The reader takes variation (epoch mod V) of a sample with V variations (mgds cycles them in order; its exact rule is
+unpinned) and emits the concept's loss_weight.
 The reader yields the reference batch contract (DataLoaderText2ImageMixin._output_modules_from_out_names),
 one resolution per GLOBAL batch, each DP rank taking its slice (aspect_bucketing.rank_slice),
 with one batch prefetched on a host thread into pinned memory.
@@ -32,6 +43,7 @@ import torch
 import torch.nn.functional as F
 from safetensors.torch import load_file, save_file
 
+from . import augment as A
 from .aspect_bucketing import AspectBucketing, aspect_batches, crop_offset, rank_slice
 
 INDEX = "index.json"
@@ -66,9 +78,23 @@ def latent_mask(mask: torch.Tensor, scale_res, crop_res, offset, size) -> torch.
     """[1, H, W] mask -> [1, h, w] latent mask: the image's scale_crop, then the downscale to the latent grid
     `size` -- mgds ScaleImage(factor 0.125) for the 8x VAEs (StableDiffusionXLBaseDataLoader.py:70) -- as the same
     antialiased bilinear resize, clamped to [0, 1]."""
-    m = scale_crop(mask, scale_res, crop_res, offset)
+    return mask_to_latent_grid(scale_crop(mask, scale_res, crop_res, offset), size)
+
+
+def mask_to_latent_grid(m: torch.Tensor, size) -> torch.Tensor:
+    """[1, H, W] cropped mask -> [1, h, w] on the latent grid `size`"""
     m = F.interpolate(m[None], size=tuple(size), mode="bilinear", antialias=True, align_corners=False)[0]
     return m.clamp(0.0, 1.0).contiguous()
+
+
+def scale_only(img: torch.Tensor, scale_res) -> torch.Tensor:
+    """the resize of scale_crop without the crop: what the device augmentations crop from"""
+    x = F.interpolate(img[None], size=tuple(scale_res), mode="bilinear", antialias=True, align_corners=False)[0]
+    return x.clamp(0.0, 1.0).contiguous()
+
+
+def variation_file(i: int, v: int) -> str:
+    return f"{i:08d}.safetensors" if v == 0 else f"{i:08d}.v{v}.safetensors"
 
 
 def scale_crop(img: torch.Tensor, scale_res, crop_res, offset):
@@ -80,19 +106,54 @@ def scale_crop(img: torch.Tensor, scale_res, crop_res, offset):
 
 class LatentCacheWriter:
     def __init__(self, encode_fn, cache_dir: str, bucketing, device, encode_batch: int = 8, rank: int = 0,
-                 text_fn=None, concepts=None):
+                 text_fn=None, concepts=None, augment_fn=None):
         """encode_fn: [B, 3, H, W] fp32 [0, 1] on `device` -> latent NHWC fp32 [B, H/8, W/8, C]
         (module.vae.AutoencoderKLEncoder.encode).  text_fn (optional): {name: int64 token ids [B, T]}
         on `device` -> {cache key: [B, ...]} (module.text_encoder.encode_sdxl_text & co.), applied to
-        samples that carry "tokens" -- the reference's text-encoder caching step."""
+        samples that carry "tokens" -- the reference's text-encoder caching step.
+        augment_fn(entries, src, out_numel, H, W) -> flat fp32 on src's device: the image augmentations of the rows
+        that ask for them (default: the HIP kernel, augment.device_augment); never called for the other rows."""
         self.encode_fn, self.cache_dir, self.bucketing = encode_fn, cache_dir, bucketing
         self.device, self.encode_batch, self.rank = torch.device(device), encode_batch, rank
         self.text_fn = text_fn
         self.concepts = concepts   # the validation cache: {name, path, seed} of the concepts its samples index
+        self.augment_fn = augment_fn or A.device_augment
+
+    def _augmented(self, rows, res):
+        """rows that carry augmentation parameters (p[10], one dict per variation): each scaled image (and mask) is
+        uploaded once, every variation is made by one augment_fn call and encoded.  -> {(sample, variation): latent},
+        {(sample, variation): cropped mask [1, H, W]}"""
+        H, W = res
+        planes, entries, masks, keys, off = [], [], [], [], 0
+        for p in rows:
+            img = scale_only(p[1], p[3])
+            src_off, off = off, off + img.numel()
+            planes.append(img.reshape(-1))
+            m_off = None
+            if p[8] is not None:
+                m = scale_only(p[8], p[3])
+                m_off, off = off, off + m.numel()
+                planes.append(m.reshape(-1))
+            for v, prm in enumerate(p[10]):
+                keys.append((p[0], v))
+                entries.append(A.entry(prm, src_off, len(entries) * 3 * H * W, 3, p[3], res))
+                if m_off is not None:   # the image's crop, flip and rotation; no colour stage
+                    masks.append(((p[0], v), prm, m_off, p[3]))
+        n = len(entries)
+        for j, (_, prm, m_off, scale_res) in enumerate(masks):
+            entries.append(A.entry(prm, m_off, (n * 3 + j) * H * W, 1, scale_res, res, colour=False))
+        out = self.augment_fn(entries, torch.cat(planes).to(self.device), (n * 3 + len(masks)) * H * W, H, W)
+        imgs = out[:n * 3 * H * W].view(n, 3, H, W)
+        lat = torch.cat([self.encode_fn(imgs[a:a + self.encode_batch]).float().cpu()
+                         for a in range(0, n, self.encode_batch)])
+        cropped = out[n * 3 * H * W:].view(len(masks), 1, H, W).float().cpu()
+        return dict(zip(keys, lat)), {m[0]: c for m, c in zip(masks, cropped)}
 
     def write(self, samples):
         """samples: iterable of dicts {"image": PIL / tensor, optional "text": {name: tensor}, optional "mask":
-        PIL 'L' image / HW uint8 / [1, H, W] float in [0, 1], cached as latent_mask}.
+        PIL 'L' image / HW uint8 / [1, H, W] float in [0, 1], cached as latent_mask, optional "augment": {"image": the
+        concept's image dict, "seed": the concept's, "index": the image's within its concept, "variations"}, optional
+        "loss_weight": the concept's}.
         Returns the number of cached samples."""
         os.makedirs(self.cache_dir, exist_ok=True)
         prepared = []
@@ -102,8 +163,12 @@ class LatentCacheWriter:
             scale_res, crop_res = self.bucketing.bucket_for(h, w)
             off = crop_offset(scale_res, crop_res)
             mask = _to_mask01(s["mask"]) if s.get("mask") is not None else None
+            aug, params = s.get("augment"), None
+            if aug and (int(aug.get("variations", 1)) > 1 or A.enabled(aug.get("image"))):
+                params = [A.draw(aug.get("image"), aug.get("seed", 0), aug.get("index", i), v, scale_res, crop_res)
+                          for v in range(int(aug.get("variations", 1)))]
             prepared.append((i, img, (h, w), scale_res, crop_res, off, dict(s.get("text") or {}), s.get("tokens"),
-                             mask, s.get("concept_index")))
+                             mask, s.get("concept_index"), params, float(s.get("loss_weight", 1.0))))
         by_res: dict = {}
         for p in prepared:
             by_res.setdefault(tuple(p[4]), []).append(p)
@@ -112,8 +177,14 @@ class LatentCacheWriter:
             group = by_res[res]
             for k in range(0, len(group), self.encode_batch):
                 chunk = group[k:k + self.encode_batch]
-                imgs = torch.stack([scale_crop(p[1], p[3], p[4], p[5]) for p in chunk]).to(self.device)
-                lat = self.encode_fn(imgs).float().cpu()
+                plain = [p for p in chunk if p[10] is None]
+                lats, crops = {}, {}
+                if plain:
+                    imgs = torch.stack([scale_crop(p[1], p[3], p[4], p[5]) for p in plain]).to(self.device)
+                    lats = {(p[0], 0): l_ for p, l_ in zip(plain, self.encode_fn(imgs).float().cpu())}
+                if len(plain) < len(chunk):
+                    more, crops = self._augmented([p for p in chunk if p[10] is not None], res)
+                    lats.update(more)
                 tok = [p for p in chunk if p[7] is not None]
                 if tok and self.text_fn is not None:
                     names = list(tok[0][7])
@@ -121,19 +192,33 @@ class LatentCacheWriter:
                                                            for p in tok]).to(self.device) for n in names})
                     for j, p in enumerate(tok):
                         p[6].update({k2: v[j].to(torch.bfloat16) for k2, v in states.items()})
-                for p, l_ in zip(chunk, lat):
+                for p in chunk:
                     i = p[0]
+                    l_ = lats[(i, 0)]
+                    offset = p[5] if p[10] is None else (p[10][0]["y0"], p[10][0]["x0"])
                     rec = {"latent_image": l_.contiguous(),
                            "original_resolution": torch.tensor(p[2], dtype=torch.int64),
-                           "crop_offset": torch.tensor(p[5], dtype=torch.int64),
+                           "crop_offset": torch.tensor(offset, dtype=torch.int64),
                            "crop_resolution": torch.tensor(p[4], dtype=torch.int64)}
                     rec.update({k2: v.detach().cpu().contiguous() for k2, v in p[6].items()})
                     if p[8] is not None:   # on the latent's own grid: crop_res / 8 for the 8x VAEs
-                        rec["latent_mask"] = latent_mask(p[8], p[3], p[4], p[5], l_.shape[:2])
-                    fn = f"{i:08d}.safetensors"
+                        rec["latent_mask"] = (latent_mask(p[8], p[3], p[4], p[5], l_.shape[:2]) if p[10] is None
+                                              else mask_to_latent_grid(crops[(i, 0)], l_.shape[:2]))
+                    fn = variation_file(i, 0)
                     if self.rank == 0:
                         save_file(rec, os.path.join(self.cache_dir, fn))
                     index[i] = {"file": fn, "crop_resolution": list(p[4])}
+                    for v in range(1, len(p[10] or ())):   # only what differs from variation 0
+                        lv = lats[(i, v)]
+                        var = {"latent_image": lv.contiguous(),
+                               "crop_offset": torch.tensor((p[10][v]["y0"], p[10][v]["x0"]), dtype=torch.int64)}
+                        if p[8] is not None:
+                            var["latent_mask"] = mask_to_latent_grid(crops[(i, v)], lv.shape[:2])
+                        if self.rank == 0:
+                            save_file(var, os.path.join(self.cache_dir, variation_file(i, v)))
+                        index[i].setdefault("variations", []).append(variation_file(i, v))
+                    if p[11] != 1.0:
+                        index[i]["loss_weight"] = p[11]
                     if p[9] is not None:
                         index[i]["concept_index"] = int(p[9])
         if self.rank == 0:
@@ -163,6 +248,7 @@ class LatentCacheDataLoader:
         self.concepts = meta.get("concepts", [])   # {name, path, seed} per concept index (validation caches)
         self.cache_dir, self.batch_size, self.device = cache_dir, batch_size, torch.device(device)
         self.seed, self.rank, self.world, self.epoch = seed, rank, world, -1
+        self.variation_epoch = None
         self.text_defaults = text_defaults or {}
         self.prefetch = prefetch
         self.require_mask = require_mask
@@ -195,8 +281,29 @@ class LatentCacheDataLoader:
             return len(aspect_batches(res, self.batch_size * self.world, self.seed, 0))
         return len(self._batches)
 
+    def set_variation_epoch(self, epoch: int):
+        """the trainer's own (restored) epoch number: a resumed run reads the variations the uninterrupted run
+        would have read.  Without it the loader's epoch count is used."""
+        self.variation_epoch = int(epoch)
+
+    def variation_files(self, i: int, epoch: int | None = None) -> list:
+        """the files sample i is read from in `epoch` (default: the current one): its own, then -- for variation
+        epoch mod V >= 1 of a sample with V variations -- the variation's, whose keys replace the first's"""
+        entry = self.index[i]
+        more = entry.get("variations") or []
+        if epoch is None:
+            epoch = self.epoch if self.variation_epoch is None else self.variation_epoch
+        v = max(epoch, 0) % (1 + len(more))
+        return [entry["file"]] + ([more[v - 1]] if v else [])
+
+    def _record(self, i: int) -> dict:
+        rec = {}
+        for fn in self.variation_files(i):
+            rec.update(load_file(os.path.join(self.cache_dir, fn)))
+        return rec
+
     def _load(self, idx):
-        recs = [load_file(os.path.join(self.cache_dir, self.index[i]["file"])) for i in idx]
+        recs = [self._record(i) for i in idx]
         b = len(recs)
         out = {"latent_image": torch.stack([r["latent_image"] for r in recs])}
         for k in ("original_resolution", "crop_offset", "crop_resolution"):
@@ -213,7 +320,9 @@ class LatentCacheDataLoader:
                 raise ValueError("masked_training: cache was built without masks; delete cache_dir "
                                  f"({self.cache_dir}) so it is rebuilt with them")
             out["latent_mask"] = torch.stack([r["latent_mask"] for r in recs])
-        out["loss_weight"] = torch.ones(b)
+        # the concept's loss_weight (ConceptConfig.py:197); an index without the key (every older cache) gives 1
+        out["loss_weight"] = torch.tensor([float(self.index[i].get("loss_weight", 1.0)) for i in idx],
+                                          dtype=torch.float32)
         if self.validation:
             out["concept_index"] = torch.tensor([int(self.index[i]["concept_index"]) for i in idx], dtype=torch.int32)
         if torch.cuda.is_available():

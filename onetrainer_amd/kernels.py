@@ -1641,6 +1641,30 @@ def dora_project(table: torch.Tensor, table_host, n_entries: int, e0: int, e1: i
           "otamd_dora_project")
 
 
+def image_augment(table: torch.Tensor, table_host, n_entries: int, src: torch.Tensor, out: torch.Tensor, H: int,
+                  W: int):
+    """Concept image augmentations of one encode batch (otamd_image_augment, csrc/augment.hip): every table entry
+    crops its source plane of `src` at (y0, x0), flips, rotates, then applies brightness, contrast, saturation and hue,
+    and writes [C, H, W] at its out_off of `out`.  table: device bytes of _lib.AugEntry[n_entries]; table_host: the
+    same array as a ctypes object (checked against the buffer sizes by the library before any launch).  src / out:
+    flat fp32 device tensors.  Returns out."""
+    _req(src.dtype == F32 and out.dtype == F32, "image_augment: fp32 source and output")
+    _req(all(t.is_cuda and t.is_contiguous() and t.dim() == 1 for t in (src, out)),
+         "image_augment buffers: flat contiguous device tensors")
+    _req(src.device == out.device == table.device, "image_augment: one device")
+    _req(0 <= n_entries <= 65535 and H > 0 and W > 0, "image_augment: 0 <= entries <= 65535, H, W > 0")
+    _req(table.dtype == torch.uint8 and table.is_contiguous()
+         and table.numel() == n_entries * C.sizeof(_lib.AugEntry), "image_augment table")
+    if n_entries == 0:
+        return out
+    ws = torch.empty(max(1, lib().otamd_image_augment_ws_floats(n_entries, int(H), int(W))), dtype=F32,
+                     device=out.device)
+    check(lib().otamd_image_augment(_p(table), C.cast(table_host, C.c_void_p), n_entries, int(H), int(W), _p(src),
+                                    src.numel(), _p(out), out.numel(), _p(ws), ws.numel(), stream_handle()),
+          "otamd_image_augment")
+    return out
+
+
 def cast_f32_bf16(x, out=None, accumulate=False):
     """fp32 -> out (bf16 or f32), optionally out += x."""
     _req(x.dtype == F32 and x.is_contiguous(), "f32 contiguous")

@@ -620,7 +620,10 @@ class GenericTrainer(TimedActionMixin):
             self.tensorboard = self._open_scalar_log()
         try:
             for _epoch in range(tp.epoch, cfg.epochs):
-                self.data_loader.get_data_set().start_next_epoch()
+                data = self.data_loader.get_data_set()
+                data.start_next_epoch()
+                if hasattr(data, "set_variation_epoch"):   # cached image variations cycle with the restored epoch
+                    data.set_variation_epoch(_epoch)
                 for batch in self.data_loader.get_data_loader():
                     if self._needs_backup(tp):
                         self._raise_timed(1, cfg.backup_after_unit)
