@@ -540,6 +540,27 @@ int otamd_ddpm_prologue(const void* latent, const void* noise, int lat_f32, cons
     acp, const float* sqrt_acp, const float* sqrt_1m, float sf, int B, long long HW, int C, int cpad, void*
     unet_in, void* target, int target_kind, float* scaled_out, hipStream_t s);
 
+/* replaces: the same for the mask-input (inpainting) model types, with the 9-channel UNet input of
+   BaseStableDiffusionXLSetup.py:217-263 / BaseStableDiffusionSetup.py:166-190 and mgds RandomLatentMaskRemove
+   (DataLoaderText2ImageMixin.py:270-276), one launch.  Beside otamd_ddpm_prologue's arguments (C = 4, cpad = 16,
+   target_kind 0 / 1): latent_mask f32 [B, HW], cond (the conditioning latent, unscaled) NHWC [B, HW, 4] of the
+   latent's dtype, blank f32 [HW, 4] (the latent of a fully masked image of this size), unmask int32 [B].
+   unet_in bf16 [B, HW, 16], 16-byte aligned: 0..3 as otamd_ddpm_prologue, 4 the mask (1 where unmask[b] != 0),
+   5..8 bf16(float(cond) * sf) (bf16(blank * sf) where unmask[b] != 0), 9..15 zero.  mask_out (nullable) f32 [B, HW]:
+   the mask as written to channel 4, unrounded (the loss mask of masked training). */
+int otamd_inpaint_prologue(const void* latent, const void* noise, int lat_f32, const int* timestep, const float*
+    acp, const float* sqrt_acp, const float* sqrt_1m, float sf, int B, long long HW, int C, int cpad, const float*
+    latent_mask, const void* cond, const float* blank, const int* unmask, void* unet_in, void* target,
+    int target_kind, float* scaled_out, float* mask_out, hipStream_t s);
+/* the draw of mgds RandomLatentMaskRemove: out[i] = u < probability for sample sample0 + i of the global batch
+   (Philox stream 8, counter = the sample's index, u in (0, 1) held below 1) */
+int otamd_inpaint_unmask(int* out, int n, long long sample0, unsigned long long seed, float probability,
+    hipStream_t s);
+/* replaces: mgds GenerateMaskedConditioningImage (DataLoaderText2ImageMixin.py:237), on the VAE encoder's own input:
+   out = bf16(float(x) * (1 - mask)), x / out NHWC bf16 [npix, cpad] in [-1, 1] (cpad % 8 == 0, 16-byte aligned),
+   mask f32 [npix] in [0, 1] */
+int otamd_masked_conditioning(const void* x, const float* mask, long long npix, int cpad, void* out, hipStream_t s);
+
 /* replaces: BaseFluxSetup.predict scale/shift + ModelSetupFlowMatchingMixin._add_noise_discrete (ModelSetupFlowMatchingMixin.py:14-39) + flow target (BaseFluxSetup.py:307) */
 int otamd_flow_prologue(const void* latent, const void* noise, int lat_f32, const int* timestep, float sf,
     float shift_factor, int num_t, int B, long long HW, int C, int cpad, void* model_in, void* target,

@@ -301,6 +301,10 @@ SIGNATURES: dict[str, list] = {
     "otamd_diffusion_loss": [VP, I, VP, I, VP, I, LL, I, F, F, F, F, I, F, VP, VP, VP, VP, I, F, I, I, F, VP, LL, VP,
                              VP, VP, VP],
     "otamd_diffusion_loss_grad": [VP, I, VP, I, VP, I, LL, I, F, VP, VP, VP, VP],
+    # inpaint.hip
+    "otamd_inpaint_prologue": [VP, VP, I, VP, VP, VP, VP, F, I, LL, I, I, VP, VP, VP, VP, VP, VP, I, VP, VP, VP],
+    "otamd_inpaint_unmask": [VP, I, LL, U64, F, VP],
+    "otamd_masked_conditioning": [VP, VP, LL, I, VP, VP],
     # validation.hip
     "otamd_validation_accumulate": [VP, VP, VP, I, I, VP, VP],
     # sampler.hip

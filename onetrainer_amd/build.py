@@ -35,6 +35,7 @@ EXTRA = {
     "adamw8bit.hip": ["-ffp-contract=off"],
     "diffusion.hip": ["-ffp-contract=off"],
     "augment.hip": ["-ffp-contract=off"],
+    "inpaint.hip": ["-ffp-contract=off"],
     "ema.hip": ["-ffp-contract=off"],
     "sampler.hip": ["-ffp-contract=off"],
     # no NaN canonicalisation (v_max_f32 x, x) in front of every fmaxf on an MFMA result: one extra

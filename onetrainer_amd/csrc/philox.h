@@ -2,7 +2,8 @@
 // of every device draw of this library.  Counter = (index lo, index hi, stream id, tag), key = the 64-bit seed.
 // Stream ids in use: 1 noise, 2 timestep uniform, 3 timestep normal, 4 offset noise, 5 perturbation noise
 // (diffusion.hip), 6 LoRA dropout (lora_dropout.hip), 7 the initial latent of a training sample
-// (modelSampler/StableDiffusionSampler.py, keyed by the sample's seed).
+// (modelSampler/StableDiffusionSampler.py, keyed by the sample's seed), 8 mask removal of the inpainting models
+// (inpaint.hip).
 #pragma once
 #include "common.h"
 

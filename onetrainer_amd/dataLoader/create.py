@@ -11,8 +11,12 @@ trainer, on this build's latent cache (dataLoader/latent_cache.py).
     loader with the base weights), write the cache on rank 0, then read it;
   * under masked_training every image is paired with <stem>-masklabel.png (DataLoaderText2ImageMixin.py:62,
     85-86; all ones when the file is missing), cached as latent_mask and required from the cache.  The
-    per-concept mask augmentations (RandomCircularMaskShrink / RandomMaskRotateCrop, :122-135) are refused;
-    unmasked_probability only acts on mask-input (inpainting) model types (:287-288), which are not loaded.
+    per-concept mask augmentations (RandomCircularMaskShrink / RandomMaskRotateCrop, :122-135) are refused.
+  * for the mask-input (inpainting) model types (util/model_type.py) the mask is loaded whether masked_training is on
+    or off (StableDiffusionBaseDataLoader.py:80,99), and the cache also holds latent_conditioning_image -- the VAE
+    mean of image * (1 - mask) (mgds GenerateMaskedConditioningImage, :236-246; K.masked_conditioning on the
+    encoder's own input) -- and one blank latent per bucket shape; unmasked_probability (:270-276, :287-288) is
+    drawn per step by the model setup, not here.  custom_conditioning_image is refused.
   * every training row carries its concept's image dict, seed, index within the concept, image_variations and
     loss_weight (concept_extras): the writer augments on the device and caches the variations (dataLoader/augment.py,
     csrc/augment.hip); the validation cache gets no augmentation and one variation.
@@ -27,6 +31,7 @@ import os
 import torch
 
 from ..util.config.plain import plain, value
+from ..util.model_type import has_mask_input
 from .latent_cache import INDEX, LatentCacheDataLoader, LatentCacheWriter, default_bucketing
 
 IMAGE_EXT = (".png", ".jpg", ".jpeg", ".webp", ".bmp", ".tif", ".tiff")
@@ -164,10 +169,21 @@ def mask_path(img_path: str) -> str | None:
     return p if os.path.isfile(p) else None
 
 
+def wants_mask(cfg) -> bool:
+    """the samples carry a mask: masked training, or a model type that takes the mask as an input"""
+    return bool(getattr(cfg, "masked_training", False)) or has_mask_input(getattr(cfg, "model_type", None))
+
+
+def check_conditioning(cfg) -> None:
+    if getattr(cfg, "custom_conditioning_image", False):
+        raise NotImplementedError("custom_conditioning_image: conditioning images from <stem>-condlabel files are "
+                                  "not built (an inpainting model's conditioning image is image * (1 - mask))")
+
+
 def enumerate_samples(config) -> list[tuple]:
     """(image path, caption) for every enabled training (non-validation) concept (mgds CollectPaths + caption
-    loading); under masked_training (image path, caption, mask path or None).  A -masklabel.png is never listed as
-    an image."""
+    loading); under masked_training or a mask-input model type (image path, caption, mask path or None).  A
+    -masklabel.png is never listed as an image."""
     cfg = plain(config)
     return [s for s, _ in _enumerate(cfg, _concepts(cfg))]
 
@@ -184,7 +200,8 @@ def enumerate_validation_samples(config) -> list[dict]:
 
 def _enumerate(cfg, concepts: list) -> list[tuple]:
     """(sample tuple, position of its concept in `concepts`)"""
-    masked = bool(getattr(cfg, "masked_training", False))
+    check_conditioning(cfg)
+    masked = wants_mask(cfg)
     out = []
     for ci, c in enumerate(concepts):
         if masked:
@@ -257,7 +274,7 @@ def build_cache(config, model, device, rank: int = 0, validation: bool = False) 
 
     def row(sample, tokens):
         r = {"image": Image.open(sample[0]), "tokens": tokens}
-        if len(sample) > 2:   # masked training: the -masklabel.png, one channel (a missing file = all ones)
+        if len(sample) > 2:   # masked training / mask input: the -masklabel.png, one channel (missing = all ones)
             r["mask"] = Image.open(sample[2]).convert("L") if sample[2] else Image.new("L", r["image"].size, 255)
         return r
 
@@ -275,10 +292,16 @@ def build_cache(config, model, device, rank: int = 0, validation: bool = False) 
         rows = ({**r, "concept_index": ci} for r, ci in zip(rows, concept_of))
     else:
         rows = ({**r, **x} for r, x in zip(rows, extras))
+    cond_fn = None
+    if has_mask_input(cfg.model_type):   # image * (1 - mask) on the encoder's own input, then the same encoder
+        from .. import kernels as K
+        from ..module.vae import PAD_IN
+        cond_fn = lambda im, m: model.vae_encoder.encode_nhwc(  # noqa: E731
+            K.masked_conditioning(K.image_to_nhwc(im.contiguous(), 2.0, -1.0, PAD_IN), m.contiguous()))
     writer = LatentCacheWriter(lambda im: model.vae_encoder.encode(im),
                                validation_cache_dir(cfg) if validation else cfg.cache_dir, default_bucketing(cfg),
                                device, rank=rank, text_fn=text_fn,
-                               concepts=validation_concepts(cfg) if validation else None)
+                               concepts=validation_concepts(cfg) if validation else None, cond_fn=cond_fn)
     return writer.write(rows)
 
 
@@ -296,11 +319,13 @@ def create_validation_data_loader(config, device, rank: int = 0, world: int = 1)
     if not getattr(cfg, "validation", False) or not validation_cache_ready(cfg):
         return None
     return LatentCacheDataLoader(validation_cache_dir(cfg), cfg.batch_size, device, seed=0, rank=rank, world=world,
-                                 require_mask=bool(getattr(cfg, "masked_training", False)), validation=True)
+                                 require_mask=wants_mask(cfg), validation=True,
+                                 require_conditioning=has_mask_input(getattr(cfg, "model_type", None)))
 
 
 def create_data_loader(config, model, device, rank: int = 0, world: int = 1):
     cfg = plain(config)
+    check_conditioning(cfg)
     need_train, need_validation = not cache_ready(cfg), validation_cache_needed(cfg)
     if need_train or need_validation:
         if getattr(model, "vae_encoder", None) is None:
@@ -319,4 +344,5 @@ def create_data_loader(config, model, device, rank: int = 0, world: int = 1):
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
     return LatentCacheDataLoader(cfg.cache_dir, cfg.batch_size, device, seed=0, rank=rank, world=world,
-                                 require_mask=bool(getattr(cfg, "masked_training", False)))
+                                 require_mask=wants_mask(cfg),
+                                 require_conditioning=has_mask_input(getattr(cfg, "model_type", None)))

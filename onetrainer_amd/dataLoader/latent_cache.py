@@ -13,9 +13,15 @@ The mgds on-disk cache format is not pinned (mgds is not in this image); this bu
   <cache_dir>/<i:08d>.safetensors   latent_image [h, w, C] fp32 NHWC (VAE latent_dist.mean, unscaled; C = 4, FLUX.1 16),
                                     original_resolution / crop_offset / crop_resolution int64 [2],
                                     optional cached text states (text_encoder_*_hidden_state, pooled),
-                                    optional latent_mask [1, h, w] fp32 in [0, 1] (masked training).
+                                    optional latent_mask [1, h, w] fp32 in [0, 1] (masked training, mask-input models),
+                                    optional latent_conditioning_image [h, w, C] fp32 NHWC (mask-input models): the VAE
+                                    latent_dist.mean of image * (1 - mask), unscaled.
+  <cache_dir>/blank_<H>x<W>.safetensors   mask-input models, once per bucket shape: latent_blank [h, w, C] fp32, the
+                                    mean latent of a fully masked H x W image (all zero in the encoder's [-1, 1]);
+                                    the index names them: "blank": {"<H>x<W>": file}.
   <cache_dir>/<i:08d>.v<v>.safetensors   variation v >= 1 of sample i (concept.image_variations): only what differs
-                                    from variation 0 -- latent_image, crop_offset, latent_mask.  Text states are
+                                    from variation 0 -- latent_image, crop_offset, latent_mask,
+                                    latent_conditioning_image.  Text states are
                                     cached once per image, in the sample's own file.
 Images are scaled / cropped on the host (data-loader work, as in mgds' worker threads), encoded on
 the GPU by the HIP VAE in same-resolution batches, and written by rank 0 only.
@@ -93,6 +99,10 @@ def scale_only(img: torch.Tensor, scale_res) -> torch.Tensor:
     return x.clamp(0.0, 1.0).contiguous()
 
 
+def blank_file(res) -> str:
+    return f"blank_{int(res[0])}x{int(res[1])}.safetensors"
+
+
 def variation_file(i: int, v: int) -> str:
     return f"{i:08d}.safetensors" if v == 0 else f"{i:08d}.v{v}.safetensors"
 
@@ -106,23 +116,27 @@ def scale_crop(img: torch.Tensor, scale_res, crop_res, offset):
 
 class LatentCacheWriter:
     def __init__(self, encode_fn, cache_dir: str, bucketing, device, encode_batch: int = 8, rank: int = 0,
-                 text_fn=None, concepts=None, augment_fn=None):
+                 text_fn=None, concepts=None, augment_fn=None, cond_fn=None):
         """encode_fn: [B, 3, H, W] fp32 [0, 1] on `device` -> latent NHWC fp32 [B, H/8, W/8, C]
         (module.vae.AutoencoderKLEncoder.encode).  text_fn (optional): {name: int64 token ids [B, T]}
         on `device` -> {cache key: [B, ...]} (module.text_encoder.encode_sdxl_text & co.), applied to
         samples that carry "tokens" -- the reference's text-encoder caching step.
         augment_fn(entries, src, out_numel, H, W) -> flat fp32 on src's device: the image augmentations of the rows
-        that ask for them (default: the HIP kernel, augment.device_augment); never called for the other rows."""
+        that ask for them (default: the HIP kernel, augment.device_augment); never called for the other rows.
+        cond_fn (mask-input models): ([B, 3, H, W] fp32 [0, 1], [B, 1, H, W] fp32 mask) on `device` -> the latent of
+        the conditioning image image * (1 - mask), NHWC fp32 like encode_fn's.  With it every sample carries a mask
+        (all ones when it brings none), every record a latent_conditioning_image, and every bucket shape a blank."""
         self.encode_fn, self.cache_dir, self.bucketing = encode_fn, cache_dir, bucketing
         self.device, self.encode_batch, self.rank = torch.device(device), encode_batch, rank
         self.text_fn = text_fn
         self.concepts = concepts   # the validation cache: {name, path, seed} of the concepts its samples index
         self.augment_fn = augment_fn or A.device_augment
+        self.cond_fn = cond_fn
 
     def _augmented(self, rows, res):
         """rows that carry augmentation parameters (p[10], one dict per variation): each scaled image (and mask) is
         uploaded once, every variation is made by one augment_fn call and encoded.  -> {(sample, variation): latent},
-        {(sample, variation): cropped mask [1, H, W]}"""
+        {(sample, variation): cropped mask [1, H, W]}, {(sample, variation): conditioning latent} (cond_fn only)"""
         H, W = res
         planes, entries, masks, keys, off = [], [], [], [], 0
         for p in rows:
@@ -146,8 +160,14 @@ class LatentCacheWriter:
         imgs = out[:n * 3 * H * W].view(n, 3, H, W)
         lat = torch.cat([self.encode_fn(imgs[a:a + self.encode_batch]).float().cpu()
                          for a in range(0, n, self.encode_batch)])
-        cropped = out[n * 3 * H * W:].view(len(masks), 1, H, W).float().cpu()
-        return dict(zip(keys, lat)), {m[0]: c for m, c in zip(masks, cropped)}
+        cropped_dev = out[n * 3 * H * W:].view(len(masks), 1, H, W)
+        conds = {}
+        if self.cond_fn is not None:   # every row has a mask here, so masks and entries share their order
+            cl = torch.cat([self.cond_fn(imgs[a:a + self.encode_batch], cropped_dev[a:a + self.encode_batch])
+                            .float().cpu() for a in range(0, n, self.encode_batch)])
+            conds = dict(zip(keys, cl))
+        cropped = cropped_dev.float().cpu()
+        return dict(zip(keys, lat)), {m[0]: c for m, c in zip(masks, cropped)}, conds
 
     def write(self, samples):
         """samples: iterable of dicts {"image": PIL / tensor, optional "text": {name: tensor}, optional "mask":
@@ -163,6 +183,8 @@ class LatentCacheWriter:
             scale_res, crop_res = self.bucketing.bucket_for(h, w)
             off = crop_offset(scale_res, crop_res)
             mask = _to_mask01(s["mask"]) if s.get("mask") is not None else None
+            if mask is None and self.cond_fn is not None:
+                mask = torch.ones((1, h, w), dtype=torch.float32)
             aug, params = s.get("augment"), None
             if aug and (int(aug.get("variations", 1)) > 1 or A.enabled(aug.get("image"))):
                 params = [A.draw(aug.get("image"), aug.get("seed", 0), aug.get("index", i), v, scale_res, crop_res)
@@ -173,18 +195,28 @@ class LatentCacheWriter:
         for p in prepared:
             by_res.setdefault(tuple(p[4]), []).append(p)
         index = [None] * len(prepared)
+        blanks = {}
         for res in sorted(by_res):
             group = by_res[res]
+            if self.cond_fn is not None:   # the latent of a fully masked image: 0.5 in [0, 1] is 0 in [-1, 1]
+                blank = self.encode_fn(torch.full((1, 3) + tuple(res), 0.5, device=self.device)).float().cpu()[0]
+                blanks[f"{res[0]}x{res[1]}"] = blank_file(res)
+                if self.rank == 0:
+                    save_file({"latent_blank": blank.contiguous()}, os.path.join(self.cache_dir, blank_file(res)))
             for k in range(0, len(group), self.encode_batch):
                 chunk = group[k:k + self.encode_batch]
                 plain = [p for p in chunk if p[10] is None]
-                lats, crops = {}, {}
+                lats, crops, conds = {}, {}, {}
                 if plain:
                     imgs = torch.stack([scale_crop(p[1], p[3], p[4], p[5]) for p in plain]).to(self.device)
                     lats = {(p[0], 0): l_ for p, l_ in zip(plain, self.encode_fn(imgs).float().cpu())}
+                    if self.cond_fn is not None:
+                        ms = torch.stack([scale_crop(p[8], p[3], p[4], p[5]) for p in plain]).to(self.device)
+                        conds = {(p[0], 0): c for p, c in zip(plain, self.cond_fn(imgs, ms).float().cpu())}
                 if len(plain) < len(chunk):
-                    more, crops = self._augmented([p for p in chunk if p[10] is not None], res)
+                    more, crops, more_conds = self._augmented([p for p in chunk if p[10] is not None], res)
                     lats.update(more)
+                    conds.update(more_conds)
                 tok = [p for p in chunk if p[7] is not None]
                 if tok and self.text_fn is not None:
                     names = list(tok[0][7])
@@ -204,6 +236,8 @@ class LatentCacheWriter:
                     if p[8] is not None:   # on the latent's own grid: crop_res / 8 for the 8x VAEs
                         rec["latent_mask"] = (latent_mask(p[8], p[3], p[4], p[5], l_.shape[:2]) if p[10] is None
                                               else mask_to_latent_grid(crops[(i, 0)], l_.shape[:2]))
+                    if self.cond_fn is not None:
+                        rec["latent_conditioning_image"] = conds[(i, 0)].contiguous()
                     fn = variation_file(i, 0)
                     if self.rank == 0:
                         save_file(rec, os.path.join(self.cache_dir, fn))
@@ -214,6 +248,8 @@ class LatentCacheWriter:
                                "crop_offset": torch.tensor((p[10][v]["y0"], p[10][v]["x0"]), dtype=torch.int64)}
                         if p[8] is not None:
                             var["latent_mask"] = mask_to_latent_grid(crops[(i, v)], lv.shape[:2])
+                        if self.cond_fn is not None:
+                            var["latent_conditioning_image"] = conds[(i, v)].contiguous()
                         if self.rank == 0:
                             save_file(var, os.path.join(self.cache_dir, variation_file(i, v)))
                         index[i].setdefault("variations", []).append(variation_file(i, v))
@@ -224,7 +260,8 @@ class LatentCacheWriter:
         if self.rank == 0:
             with open(os.path.join(self.cache_dir, INDEX), "w") as f:
                 json.dump({"version": 1, "samples": index,
-                           **({} if self.concepts is None else {"concepts": self.concepts})}, f)
+                           **({} if self.concepts is None else {"concepts": self.concepts}),
+                           **({"blank": blanks} if self.cond_fn is not None else {})}, f)
         return len(index)
 
 
@@ -234,9 +271,12 @@ class LatentCacheDataLoader:
 
     def __init__(self, cache_dir: str, batch_size: int, device, seed: int = 0, rank: int = 0, world: int = 1,
                  text_defaults: dict | None = None, prefetch: bool = True, require_mask: bool = False,
-                 validation: bool = False):
-        """require_mask (masked training): batches carry latent_mask [B, 1, h, w]; a cached record without
-        one is an error.  Otherwise a cached mask is not emitted.
+                 validation: bool = False, require_conditioning: bool = False):
+        """require_mask (masked training, mask-input models): batches carry latent_mask [B, 1, h, w]; a cached record
+        without one is an error.  Otherwise a cached mask is not emitted.
+        require_conditioning (mask-input models): batches carry latent_conditioning_image [B, C, h, w] (a view of
+        NHWC storage, like latent_image) and latent_blank [h, w, C], the blank latent of the batch's bucket shape; a
+        cache without either is an error.
         validation (the held-out set's cache): every pass emits every sample exactly once in a fixed order -- the
         buckets in ascending resolution, cache index order within a bucket, no shuffle, nothing dropped, a short
         last batch run short -- and each batch carries concept_index int32 [B] on the device (and
@@ -252,6 +292,9 @@ class LatentCacheDataLoader:
         self.text_defaults = text_defaults or {}
         self.prefetch = prefetch
         self.require_mask = require_mask
+        self.require_conditioning = require_conditioning
+        self.blank_files = meta.get("blank") or {}
+        self._blanks: dict = {}
         self._batches = []
 
     # BaseDataLoader.get_data_set() -> MGDS-like
@@ -320,6 +363,15 @@ class LatentCacheDataLoader:
                 raise ValueError("masked_training: cache was built without masks; delete cache_dir "
                                  f"({self.cache_dir}) so it is rebuilt with them")
             out["latent_mask"] = torch.stack([r["latent_mask"] for r in recs])
+        if self.require_conditioning:
+            res = "x".join(str(int(v)) for v in self.index[idx[0]]["crop_resolution"])
+            if any("latent_conditioning_image" not in r for r in recs) or res not in self.blank_files:
+                raise ValueError("mask-input model type: cache was built without conditioning latents; delete "
+                                 f"cache_dir ({self.cache_dir}) so it is rebuilt with them")
+            out["latent_conditioning_image"] = torch.stack([r["latent_conditioning_image"] for r in recs])
+            if res not in self._blanks:
+                self._blanks[res] = load_file(os.path.join(self.cache_dir, self.blank_files[res]))["latent_blank"]
+            out["latent_blank"] = self._blanks[res].clone()
         # the concept's loss_weight (ConceptConfig.py:197); an index without the key (every older cache) gives 1
         out["loss_weight"] = torch.tensor([float(self.index[i].get("loss_weight", 1.0)) for i in idx],
                                           dtype=torch.float32)
@@ -342,6 +394,8 @@ class LatentCacheDataLoader:
                 dev[k] = v.to(self.device, non_blocking=True)
         # the reference's [B, C, h, w] contract, as a view of the cached channels-last (NHWC) storage
         dev["latent_image"] = dev["latent_image"].permute(0, 3, 1, 2)
+        if "latent_conditioning_image" in dev:
+            dev["latent_conditioning_image"] = dev["latent_conditioning_image"].permute(0, 3, 1, 2)
         dev["concept_type"] = ["VALIDATION" if self.validation else "STANDARD"] * dev["latent_image"].shape[0]
         return dev
 

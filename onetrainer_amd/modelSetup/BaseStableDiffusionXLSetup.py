@@ -22,6 +22,7 @@ import torch
 from .. import kernels as K
 from ..module import functional as Fn
 from ..util.config.plain import plain
+from ..util.model_type import has_mask_input
 from ..util.timestep_table import TABLE_DISTS, TimestepTables
 
 LOSS_FN = {"CONSTANT": 0, "MIN_SNR_GAMMA": 1, "DEBIASED_ESTIMATION": 2, "P2": 3}
@@ -66,11 +67,14 @@ def plain_mse(plan: dict) -> bool:
     return not plan["masked"] and plan["mae_strength"] == 0 and plan["log_cosh_strength"] == 0
 
 
-def loss_mask(batch: dict, plan: dict, device):
+def loss_mask(batch: dict, plan: dict, device, data: dict | None = None):
     """batch["latent_mask"] [B, 1, h, w] as the loss kernel reads it (f32, contiguous, on the device), or None
-    when the plan is unmasked"""
+    when the plan is unmasked.  A mask-input model's predict() hands over the mask it fed the UNet (all ones where the
+    step removed a sample's mask) as data["_loss_mask"]: the loss is weighted by that one."""
     if not plan["masked"]:
         return None
+    if data is not None and data.get("_loss_mask") is not None:
+        return data["_loss_mask"]
     if "latent_mask" not in batch:
         raise KeyError("latent_mask: masked_training is on, but the batch carries no 'latent_mask' "
                        "(a cache built without masks?)")
@@ -128,7 +132,7 @@ def per_sample_losses(model, batch, data, plan, C, device, coeffs, v_pred, num_t
         return K.mse_loss(pred, target, lw, mse_strength=plan["mse_strength"], scale=scale, loss_fn=plan["loss_fn"],
                           gamma=plan["gamma"], v_pred=v_pred, ga=1.0, timestep=data["timestep"], coeffs=coeffs,
                           num_t=num_t)[2]
-    return K.diffusion_loss(pred, target, loss_mask(batch, plan, device), lw, mse_strength=plan["mse_strength"],
+    return K.diffusion_loss(pred, target, loss_mask(batch, plan, device, data), lw, mse_strength=plan["mse_strength"],
                             mae_strength=plan["mae_strength"], log_cosh_strength=plan["log_cosh_strength"],
                             unmasked_weight=plan["unmasked_weight"], normalize=plan["normalize"], scale=scale,
                             loss_fn=plan["loss_fn"], gamma=plan["gamma"], v_pred=v_pred, ga=1.0,
@@ -189,7 +193,8 @@ class BaseStableDiffusionXLSetup:
         self.debug_mode = debug_mode
         self.dp_rank = dp_rank
         self.dp_world = dp_world
-        self.graph_inputs = None   # (noise, timestep) drawn outside a captured step (trainer/step_graph.py)
+        # (noise, timestep[, unmask: mask-input models]) drawn outside a captured step (trainer/step_graph.py)
+        self.graph_inputs = None
         self.timestep_tables = TimestepTables()   # COS_MAP / SIGMOID cumulative tables on the device
 
     # ------------------------------------------------------------------------------------------
@@ -255,6 +260,14 @@ class BaseStableDiffusionXLSetup:
         else:
             timestep = draw_timesteps(self.timestep_tables, config, B, batch_seed, sample0, N, config.timestep_shift,
                                       lat.device, out=None if out is None else out[1])
+        if has_mask_input(config.model_type):
+            # mgds RandomLatentMaskRemove (DataLoaderText2ImageMixin.py:270-276): which samples lose their mask this
+            # step -- Philox stream 8 under the same seed and global-batch counter, written beside noise and timestep
+            # outside a captured step; the validation pass removes none
+            p = 0.0 if deterministic else float(getattr(config, "unmasked_probability", 0.0))
+            unmask = K.inpaint_unmask(B, batch_seed, p, sample0=sample0, device=lat.device,
+                                      out=None if out is None else out[2])
+            return noise, timestep, unmask
         return noise, timestep
 
     def predict(self, model, batch: dict, config, train_progress, *, deterministic: bool = False,
@@ -267,13 +280,27 @@ class BaseStableDiffusionXLSetup:
         sf = model.vae.config["scaling_factor"]
         ehs, pooled = self._text(model, batch, config, rand, B, per_sample)
         if self.graph_inputs is not None and not per_sample:
-            noise, timestep = self.graph_inputs
+            inputs = self.graph_inputs
         else:
-            noise, timestep = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic,
-                                               per_sample=per_sample)
+            inputs = self.step_inputs(model, batch, config, train_progress, deterministic=deterministic,
+                                      per_sample=per_sample)
+        noise, timestep = inputs[0], inputs[1]
         ptype = model.noise_scheduler.config["prediction_type"]
-        unet_in, target, _ = K.ddpm_prologue(latent, noise, timestep, model.noise_scheduler.coeffs, sf,
-                                             1 if ptype == "v_prediction" else 0)
+        eff_mask = None
+        if has_mask_input(config.model_type):
+            for key in ("latent_mask", "latent_conditioning_image", "latent_blank"):
+                if key not in batch:
+                    raise KeyError(f"{key}: model type {config.model_type} has a mask input, but the batch carries "
+                                   f"no '{key}' (a cache built without it?)")
+            cond = self._nhwc_latent(batch["latent_conditioning_image"]).to(latent.dtype)
+            unet_in, target, _, eff_mask = K.inpaint_prologue(
+                latent, noise, timestep, model.noise_scheduler.coeffs, sf, 1 if ptype == "v_prediction" else 0,
+                batch["latent_mask"].to(latent.device, torch.float32).contiguous(), cond,
+                batch["latent_blank"].to(latent.device, torch.float32).contiguous(), inputs[2],
+                want_mask=bool(config.masked_training))
+        else:
+            unet_in, target, _ = K.ddpm_prologue(latent, noise, timestep, model.noise_scheduler.coeffs, sf,
+                                                 1 if ptype == "v_prediction" else 0)
         time_ids = None
         if model.unet.cfg.addition_embed:
             time_ids = torch.stack([batch["original_resolution"][0], batch["original_resolution"][1],
@@ -286,7 +313,8 @@ class BaseStableDiffusionXLSetup:
         # calculate_loss reads directly through the private keys
         return {"loss_type": "target", "timestep": timestep,
                 "predicted": pred[..., :C].permute(0, 3, 1, 2), "target": target.permute(0, 3, 1, 2),
-                "prediction_type": ptype, "_predicted_nhwc": pred, "_target_nhwc": target}
+                "prediction_type": ptype, "_predicted_nhwc": pred, "_target_nhwc": target,
+                **({} if eff_mask is None else {"_loss_mask": eff_mask})}
 
     def calculate_loss(self, model, batch: dict, data: dict, config) -> torch.Tensor:
         plan = loss_plan(plain(config))
@@ -299,7 +327,8 @@ class BaseStableDiffusionXLSetup:
             return Fn.MSELossFn.apply(pred, target, lw, data["timestep"], model.noise_scheduler.coeffs, plan["loss_fn"],
                                       plan["gamma"], v_pred, 1.0, plan["mse_strength"], scale, 1.0 / self.dp_world)
         strengths = (plan["mse_strength"], plan["mae_strength"], plan["log_cosh_strength"])
-        return Fn.DiffusionLossFn.apply(pred, target, loss_mask(batch, plan, self.train_device), lw, data["timestep"],
+        return Fn.DiffusionLossFn.apply(pred, target, loss_mask(batch, plan, self.train_device, data), lw,
+                                        data["timestep"],
                                         model.noise_scheduler.coeffs, plan["loss_fn"], plan["gamma"], v_pred, 1.0,
                                         strengths, plan["unmasked_weight"], plan["normalize"], scale,
                                         1.0 / self.dp_world)

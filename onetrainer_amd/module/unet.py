@@ -12,8 +12,8 @@ UNet state dict (conv weights are held [Cout][kh][kw][Cin] internally and permut
 Layout choices (MI355X-first, not a translation):
   * activations NHWC: a conv's GEMM rows are pixels, and a Transformer2D's proj_in/out are
     Linears over the same [pixels, C] rows (no permutes anywhere);
-  * conv_in takes 8 input channels (4 latent + 4 zero) and conv_out emits 8 (4 + 4 zero) so
-    every operand row is a whole number of 16-byte chunks;
+  * conv_in takes 8 input channels (4 latent + 4 zero; 16 = 9 + 7 zero for a mask-input UNet, pad_in) and
+    conv_out emits 8 (4 + 4 zero) so every operand row is a whole number of 16-byte chunks;
   * to_q|to_k|to_v (self) and to_k|to_v (cross) are adjacent in the flat store: one GEMM each.
 """
 from __future__ import annotations
@@ -121,6 +121,12 @@ PAD_IN = 8    # conv_in input channels held (latent channels zero-padded)
 PAD_OUT = 8   # conv_out output channels held
 
 
+def pad_in(in_channels: int) -> int:
+    """conv_in input channels held for a UNet of `in_channels`: whole 16-byte chunks -- PAD_IN for the 4 latent
+    channels, 16 for the 9 of a mask-input (inpainting) UNet (4 latent + 1 mask + 4 conditioning latent)"""
+    return max(PAD_IN, (in_channels + 7) // 8 * 8)
+
+
 # ----------------------------------------------------------------------------------------------
 # parameter specs in forward-execution order: (name, diffusers_shape, kind, fan_in)
 def _lin(p, cin, cout, bias=True):
@@ -212,7 +218,7 @@ def _store_shape(name, shape, kind, cfg):
     if kind == "conv":
         co, ci, kh, kw = shape
         if name == "conv_in.weight":
-            ci = PAD_IN
+            ci = PAD_IN if cfg is None else pad_in(cfg.in_channels)
         if name == "conv_out.weight":
             co = PAD_OUT
         if kh == 1:
@@ -262,7 +268,7 @@ class UNet2DConditionModel:
         if kind == "conv":
             v = v.permute(0, 2, 3, 1) if v.dim() == 4 and v.shape[2] > 1 else v.reshape(v.shape[0], v.shape[1])
             if name == "conv_in.weight":
-                v = torch.nn.functional.pad(v, (0, PAD_IN - v.shape[-1]))
+                v = torch.nn.functional.pad(v, (0, pad_in(self.cfg.in_channels) - v.shape[-1]))
             if name == "conv_out.weight":
                 v = torch.nn.functional.pad(v, (0, 0, 0, 0, 0, 0, 0, PAD_OUT - v.shape[0]))
         if name == "conv_out.bias":
@@ -421,7 +427,7 @@ class UNet2DConditionModel:
         return self.forward(sample, timestep, encoder_hidden_states, text_embeds, time_ids)
 
     def forward(self, sample, timestep, encoder_hidden_states, text_embeds=None, time_ids=None):
-        """sample [B,H,W,8] bf16 NHWC (latent channels zero-padded), timestep int [B] or [1],
+        """sample [B,H,W,8] bf16 NHWC (latent channels zero-padded; [B,H,W,16] for in_channels 9), timestep int [B] or [1],
         encoder_hidden_states [B,L,ctx] bf16, SDXL: text_embeds [B,1280], time_ids [B,6].
         Returns the prediction [B,H,W,8] bf16 (channels >= out_channels are zero)."""
         cfg = self.cfg

@@ -38,9 +38,11 @@ import os
 
 import torch
 
+from ..util.model_type import has_mask_input
+
 
 class _Entry:
-    __slots__ = ("graph", "batch", "noise", "timestep", "loss")
+    __slots__ = ("graph", "batch", "noise", "timestep", "inputs", "loss")
 
 
 class StepGraphs:
@@ -98,12 +100,15 @@ class StepGraphs:
         shape = tuple(setup._nhwc_latent(lat).shape)
         e.noise = torch.empty(shape, dtype=lat.dtype, device=lat.device)
         e.timestep = torch.empty(shape[0], dtype=torch.int32, device=lat.device)
+        e.inputs = (e.noise, e.timestep)
+        if has_mask_input(tr.config.model_type):   # the step's mask removals, drawn beside noise and timestep
+            e.inputs += (torch.zeros(shape[0], dtype=torch.int32, device=lat.device),)
         torch.cuda.synchronize()
         torch.cuda.empty_cache()   # the eager steps' cached blocks; the graph gets its own pool
         g = torch.cuda.CUDAGraph(keep_graph=bool(self.debug_dot))   # debug: keep the hipGraph_t for the dump
         if self.debug_dot:
             g.enable_debug_mode()
-        setup.graph_inputs = (e.noise, e.timestep)
+        setup.graph_inputs = e.inputs
         try:
             with torch.cuda.graph(g, pool=self.pool):
                 e.loss = self._body(e.batch)
@@ -133,6 +138,6 @@ class StepGraphs:
                 if dst.data_ptr() != v.data_ptr():
                     dst.copy_(v, non_blocking=True)
         tr.model_setup.step_inputs(tr.model, e.batch, tr.config, tr.model.train_progress,
-                                   out=(e.noise, e.timestep))
+                                   out=e.inputs)
         e.graph.replay()
         return e.loss.clone()

@@ -3,13 +3,16 @@ samples of SD 1.5 / SDXL, loadable from the reference's own sample JSON (`traini
 inline `samples` list of a train config.  Unknown keys are kept in `extra` and ignored.
 
 What this build's sampler does not do is refused by name when the sample configs are read (check_supported), not in
-the middle of a run: schedulers other than DDIM, sample_inpainting, frames > 1.
+the middle of a run: schedulers other than DDIM, sample_inpainting, frames > 1, and any enabled sample of a mask-input
+(inpainting) model type.
 """
 from __future__ import annotations
 
 import json
 import os
 from dataclasses import dataclass, field, fields
+
+from ..model_type import has_mask_input
 
 IMAGE_FORMATS = {"JPG": (".jpg", "JPEG"), "PNG": (".png", "PNG"), "WEBP": (".webp", "WEBP")}   # ImageFormat.py
 
@@ -99,6 +102,10 @@ def read_sample_configs(train_config) -> list[SampleConfig]:
     for s in out:
         if s.enabled:
             s.check_supported()
+    model_type = getattr(train_config, "model_type", None)
+    if has_mask_input(model_type) and any(s.enabled for s in out):
+        raise NotImplementedError(f"samples for model type {getattr(model_type, 'value', model_type)}: the sampler "
+                                  "has no mask and conditioning-image input; disable the sample definitions")
     return out
 
 

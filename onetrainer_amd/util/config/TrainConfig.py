@@ -110,9 +110,12 @@ class TrainConfig:
     loss_weight_strength: float = 5.0
     loss_scaler: str = "NONE"
     masked_training: bool = False
-    # masked training (TrainConfig.py:933-938); unmasked_probability is read by the reference's inpainting
-    # loaders only and masked_prior_preservation_weight != 0 is refused (modelSetup loss_plan)
+    # masked training (TrainConfig.py:933-938); unmasked_probability acts on the mask-input (inpainting) model types
+    # only: the chance that a step replaces a sample's mask by all ones (modelSetup step_inputs);
+    # masked_prior_preservation_weight != 0 is refused (modelSetup loss_plan), custom_conditioning_image
+    # (TrainConfig.py:939) too (dataLoader/create.py): the conditioning image is always image * (1 - mask)
     unmasked_probability: float = 0.1
+    custom_conditioning_image: bool = False
     unmasked_weight: float = 0.1
     normalize_masked_area_loss: bool = False
     masked_prior_preservation_weight: float = 0.0

@@ -9,12 +9,23 @@ from ..model.StableDiffusionXLModel import NoiseScheduler, StableDiffusionXLMode
 from ..module import unet as U
 from ..util.lr_scheduler_util import create_lr_scheduler  # noqa: F401  (re-export)
 from .config.plain import plain
+from .model_type import has_mask_input, unet_in_channels
 
-SCALING = {"STABLE_DIFFUSION_XL_10_BASE": 0.13025, "STABLE_DIFFUSION_15": 0.18215}
+SCALING = {"STABLE_DIFFUSION_XL_10_BASE": 0.13025, "STABLE_DIFFUSION_15": 0.18215,
+           "STABLE_DIFFUSION_XL_10_BASE_INPAINTING": 0.13025, "STABLE_DIFFUSION_15_INPAINTING": 0.18215}
 
 
 def is_flux(model_type: str) -> bool:
     return model_type.startswith("FLUX")
+
+
+def check_in_channels(model_type: str, in_channels: int, c0: int = 320) -> None:
+    """the UNet a checkpoint or a config declares against the model type: a 4-channel UNet under an inpainting type
+    (or a 9-channel one under a plain type) is refused by the weight that would not fit"""
+    want = unet_in_channels(model_type)
+    if (int(in_channels) != 9) == has_mask_input(model_type):
+        raise ValueError(f"conv_in.weight: shape {(c0, int(in_channels), 3, 3)} != {(c0, want, 3, 3)}: model type "
+                         f"{model_type} takes a UNet with {want} input channels")
 
 
 def create_model(config, device, seed=0, unet_config=None, prediction_type="epsilon", flux_config=None):
@@ -41,6 +52,8 @@ def create_model(config, device, seed=0, unet_config=None, prediction_type="epsi
             unet_config = U.sd15_config()
         else:
             raise NotImplementedError(f"model type {mt}")
+        unet_config.in_channels = unet_in_channels(mt)
+    check_in_channels(mt, unet_config.in_channels, unet_config.block_out_channels[0])
     unet = U.UNet2DConditionModel(unet_config, device, seed=seed, trainable=config.training_method != "LORA",
                                   master=plan.master)
     ns = NoiseScheduler(device, prediction_type=prediction_type)
