@@ -7,6 +7,7 @@ and the latent-cache writer's token -> text-state hook."""
 import pytest
 import torch
 
+import _frozen_parity as P
 from onetrainer_amd.module import text_encoder as TE
 from oracle import text_encoder as OT
 
@@ -18,6 +19,12 @@ def close(out, ref, tol=3e-2):
     err = (out - ref).abs().max().item()
     scale = ref.abs().max().item() + 1e-6
     assert err / scale < tol, f"max err {err} vs scale {scale}"
+
+
+def rows_close(got: dict, ref: dict, label):
+    """the per-row check of _frozen_parity.py (tiny configs only): every token within REL_BOUND of the float64
+    oracle, every tensor's scale within S_BOUND"""
+    P.check({k: v.float().cpu() for k, v in got.items()}, ref, label, "text")
 
 
 def _ids(B, T, vocab, seed=0):
@@ -55,6 +62,14 @@ def test_clip_encoder(dev, cfg):
         out, _ = enc.encode(ids.to(dev), default_layer=dl, layer_skip=skip, add_layer_norm=ln)
         ref, _ = OT.encode_clip(sd, ids, cfg.num_attention_heads, cfg.hidden_act, dl, skip, ln)
         close(out, ref)
+    if cfg.hidden_size == 64:
+        hs64, last64, pooled64, embeds64 = OT.clip_forward(sd, ids, cfg.num_attention_heads, cfg.hidden_act,
+                                                           dtype=torch.float64)
+        got = {f"hidden_states[{i}]": h for i, h in got_hs.items()}
+        ref = {f"hidden_states[{i}]": h for i, h in enumerate(hs64)}
+        got.update(last_hidden_state=got_last.view(3, 77, -1), pooled=p)
+        ref.update(last_hidden_state=last64, pooled=embeds64 if cfg.projection_dim else pooled64)
+        rows_close(got, ref, f"tiny CLIP projection={bool(cfg.projection_dim)}")
 
 
 @pytest.mark.parametrize("cfg", [TE.tiny_t5_config(), TE.T5Config(num_layers=1)])
@@ -66,6 +81,10 @@ def test_t5_encoder(dev, cfg):
     for i, h in got.items():
         close(h, hs[i])
     close(enc.encode(ids.to(dev)), hs[-1])
+    if cfg.d_model == 64:
+        hs64 = OT.t5_forward(_sd(enc), ids, cfg.num_heads, dtype=torch.float64)
+        rows_close({f"hidden_states[{i}]": h for i, h in got.items()},
+                   {f"hidden_states[{i}]": h for i, h in enumerate(hs64)}, "tiny T5")
 
 
 def test_family_encodes_and_cache_hook(dev, tmp_path):
@@ -83,6 +102,13 @@ def test_family_encodes_and_cache_hook(dev, tmp_path):
     _, last, pooled1, _ = OT.clip_forward(_sd(te1), ids1, 2, "quick_gelu")
     close(fl["text_encoder_1_pooled_state"], pooled1)
     close(fl["text_encoder_2_hidden_state"], OT.t5_forward(_sd(t5), ids2, 8)[-1])
+    f64 = torch.float64
+    h1, _ = OT.encode_clip(_sd(te1), ids1, 2, "quick_gelu", -2, 0, False, dtype=f64)
+    h2, pooled64 = OT.encode_clip(_sd(te2), ids2, 2, "gelu", -2, 0, False, dtype=f64)
+    rows_close(out, {"text_encoder_1_hidden_state": h1, "text_encoder_2_hidden_state": h2,
+                     "text_encoder_2_pooled_state": pooled64}, "encode_sdxl_text")
+    rows_close(fl, {"text_encoder_1_pooled_state": OT.clip_forward(_sd(te1), ids1, 2, "quick_gelu", dtype=f64)[2],
+                    "text_encoder_2_hidden_state": OT.t5_forward(_sd(t5), ids2, 8, dtype=f64)[-1]}, "encode_flux_text")
 
     from onetrainer_amd.dataLoader.aspect_bucketing import AspectBucketing
     from onetrainer_amd.dataLoader.latent_cache import LatentCacheDataLoader, LatentCacheWriter

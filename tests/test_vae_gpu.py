@@ -5,6 +5,7 @@ weights and images.  Tolerance: bf16 activations with fp32 accumulation vs fp32 
 import pytest
 import torch
 
+import _frozen_parity as P
 from onetrainer_amd import kernels as K
 from onetrainer_amd.module import vae as V
 from oracle import vae as OV
@@ -38,6 +39,13 @@ def test_vae_encode_matches_oracle(dev, cfgname, B, H, W):
     err = (lat.cpu() - ref).abs().max() / ref.abs().max()
     assert err < 3e-2, f"rel err {err}"
     assert _cos(lat.cpu(), ref) > 0.9995
+    if cfgname.startswith("tiny"):
+        # the per-row check of _frozen_parity.py: every latent pixel against the float64 oracle
+        om64 = OV.AutoencoderKLEncoder(cfg, torch.float64)
+        om64.load_state_dict({k: v.float().cpu() for k, v in enc.state_dict().items()})
+        with torch.no_grad():
+            ref64 = om64.moments((img * 2 - 1).bfloat16().float())[:, :cfg.latent_channels].permute(0, 2, 3, 1)
+        P.check({"mean": lat.cpu()}, {"mean": ref64}, f"encoder {cfgname}", "vae")
 
 
 def test_image_to_nhwc(dev):
