@@ -270,8 +270,9 @@ __global__ void __launch_bounds__(256) grad_sqnorm_kernel(const T* __restrict__ 
   long long e = c.begin + threadIdx.x * 8;
   if (sizeof(T) == 2) {
     // four 16-byte loads in flight per lane before the adds (one per iteration left the pass at ~2.1 TB/s in the
-    // step); the per-load partials are added in the same order as the one-load loop: the same bits
-    for (; e + 3 * 256 * 8 < c.end; e += 4 * 256 * 8) {
+    // step); the per-load partials are added in the same order as the one-load loop: the same bits.  Whole vectors
+    // only: a vector the tensor ends in is left to the loop below, which masks it
+    for (; e + 3 * 256 * 8 + 8 <= c.end; e += 4 * 256 * 8) {
       bf8 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const bf8*>(G + e + u * 256 * 8);
@@ -286,22 +287,19 @@ __global__ void __launch_bounds__(256) grad_sqnorm_kernel(const T* __restrict__ 
       }
     }
   }
-  // 16-byte vector body (chunk bounds are multiples of 8 elements)
+  // 16-byte vector body (a chunk begins on a multiple of 8 elements; its tensor may end inside the last vector, whose
+  // remaining lanes are the store's padding and belong to no chunk: they count as +0, whatever the padding holds)
   for (; e < c.end; e += 256 * 8) {
-    if (sizeof(T) == 2) {
-      bf8 v = *reinterpret_cast<const bf8*>(G + e);
-      float f[8];
-      unpack8(v, f);
-      float s = 0.f;
+    float f[8];
+    fs_load8<T>(G, e, f);
+    if (e + 8 > c.end) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s = fmaf(f[j], f[j], s);
-      acc += s;
-    } else {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { float f = fs_load1<T>(G, e + j); s = fmaf(f, f, s); }
-      acc += s;
+      for (int j = 1; j < 8; ++j) f[j] = e + j < c.end ? f[j] : 0.f;
     }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s = fmaf(f[j], f[j], s);
+    acc += s;
   }
   __shared__ double red[4];
   acc = wave_sum_d(acc);
@@ -326,6 +324,8 @@ __global__ void tensor_sq_kernel(const NormChunk* __restrict__ chunks, int n_chu
 
 // total_norm / clip coefficient with torch's bf16 result dtypes:
 //   per-tensor norm (bf16) -> stack -> vector_norm (bf16) -> max_norm/(norm+1e-6) (bf16) -> clamp(max=1)
+// A Python float over a tensor is Tensor.__rtruediv__, reciprocal() * max_norm: two roundings, the same bits as the
+// one division at max_norm == 1 and up to an ulp of the result's dtype apart elsewhere.
 // out[0] = clip coefficient (as float of a bf16 / f32 value), out[1] = total norm
 __global__ void clip_coef_kernel(const double* __restrict__ tensor_sq, int n_tensors, float max_norm, int bf16_grads,
                                  float* __restrict__ out) {
@@ -343,11 +343,11 @@ __global__ void clip_coef_kernel(const double* __restrict__ tensor_sq, int n_ten
     if (bf16_grads) {
       total = rbf(total);
       const float denom = rbf(total + 1e-6f);
-      coef = rbf(max_norm / denom);
-      coef = fminf(coef, 1.f);
+      coef = rbf(rbf(1.f / denom) * max_norm);
     } else {
-      coef = fminf(max_norm / (total + 1e-6f), 1.f);
+      coef = (1.f / (total + 1e-6f)) * max_norm;
     }
+    coef = coef > 1.f ? 1.f : coef;   // torch.clamp(max=1): a NaN coefficient stays NaN (fminf would return 1)
     out[0] = coef;
     out[1] = total;
   }

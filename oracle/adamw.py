@@ -110,10 +110,11 @@ def adamw_step_master(p, g_bits, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-
 
 def clip_grad_norm_f32(grads: list[np.ndarray], max_norm=1.0):
     """torch clip_grad_norm_ on fp32 grads: per-tensor fp32 norms, their fp32 2-norm, coef = max_norm / (total + 1e-6)
-    clamped to 1, in fp32.  (torch sums in fp32 with its own order; the sums here are fp64, rounded once.)"""
+    clamped to 1, in fp32.  (torch sums in fp32 with its own order; the sums here are fp64, rounded once.)  A Python
+    float over a tensor is Tensor.__rtruediv__: reciprocal() times the float, each rounded; the clamp keeps a NaN."""
     norms = np.array([np.float32(np.sqrt(np.sum(np.asarray(g, np.float64) ** 2))) for g in grads], np.float32)
     total = np.float32(np.sqrt(np.sum(norms.astype(np.float64) ** 2)))
-    coef = np.float32(min(np.float32(max_norm) / (total + np.float32(1e-6)), np.float32(1.0)))
+    coef = np.float32(min((np.float32(1.0) / (total + np.float32(1e-6))) * np.float32(max_norm), np.float32(1.0)))
     return float(total), coef
 
 
@@ -122,7 +123,7 @@ def clip_grad_norm_bf16(grads_bits: list[np.ndarray], max_norm=1.0):
     Returns (clipped grads bits, total norm, coef)."""
     norms = [rbf(np.float32(np.sqrt(np.sum(bf16_to_f32(g).astype(np.float64) ** 2)))) for g in grads_bits]
     total = rbf(np.float32(np.sqrt(np.sum(np.array(norms, np.float64) ** 2))))
-    coef = rbf(np.float32(max_norm) / rbf(total + np.float32(1e-6)))
+    coef = rbf(rbf(np.float32(1.0) / rbf(total + np.float32(1e-6))) * np.float32(max_norm))   # reciprocal() * max_norm
     coef = np.float32(min(coef, 1.0))
     out = [f32_to_bf16_bits(bf16_to_f32(g) * coef) for g in grads_bits]
     return out, float(total), float(coef)
