@@ -208,17 +208,20 @@ int otamd_gemm_args_size(void);
 /* replaces: ABI check */
 int otamd_conv_geom_size(void);
 
-/* replaces: F.scaled_dot_product_attention in diffusers Attention (attn1/attn2 of every BasicTransformerBlock) */
+/* replaces: F.scaled_dot_product_attention in diffusers Attention (attn1/attn2 of every BasicTransformerBlock).
+   Head dims Dv <= 160, Dv % 8 == 0: <= 64 and <= 128 on csrc/attention.hip, 129..160 (SD 1.5's 160-wide heads) on
+   csrc/attention_wide.hip */
 int otamd_attn_fwd(const AttnArgs* in, hipStream_t stream);
 
 /* replaces: autograd of scaled_dot_product_attention (GenericTrainer.py:693-696) */
 int otamd_attn_bwd(const AttnArgs* in, float* ws, long long ws_bytes, hipStream_t stream);
 
 /* workspace bytes otamd_attn_bwd needs for these arguments (16-byte bias records per query + split-query or
-   per-chunk dK/dV partials) */
+   per-chunk dK/dV partials; Dv > 128: one {lse, delta} pair per query, no partials) */
 long long otamd_attn_bwd_ws_bytes(const AttnArgs* in);
 
-/* bytes of the fp32 dK / dV partial slabs alone (0: none needed), the caller-owned buffer of otamd_attn_bwd_ex */
+/* bytes of the fp32 dK / dV partial slabs alone (0: none needed, always so for Dv > 128), the caller-owned buffer of
+   otamd_attn_bwd_ex */
 long long otamd_attn_bwd_slab_bytes(const AttnArgs* in);
 
 /* replaces: as otamd_attn_bwd (autograd of scaled_dot_product_attention, GenericTrainer.py:693-696), with the dK / dV
@@ -230,8 +233,8 @@ int otamd_attn_bwd_ex(const AttnArgs* in, float* ws, long long ws_bytes, float* 
 /* replaces: ABI check */
 int otamd_attn_args_size(void);
 
-/* replaces: the softmax inside F.scaled_dot_product_attention for heads wider than 128 (SD 1.5 160-wide heads,
-   v1-inference.yaml:29-44; VAE mid-block 512-wide head): P = softmax(scale S) row-wise, bf16 P, natural-log lse */
+/* replaces: the softmax inside F.scaled_dot_product_attention for heads wider than 160 (VAE mid-block 512-wide
+   head) and the materialized comparison path: P = softmax(scale S) row-wise, bf16 P, natural-log lse */
 int otamd_softmax_rows_fwd(const float* S, long long lds, void* P, long long ldp, float* lse, long long rows,
                            int ncols, int ncols_pad, float scale, hipStream_t stream);
 

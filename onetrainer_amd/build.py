@@ -43,6 +43,11 @@ EXTRA = {
     # no SLP packing of the softmax's f32 math into v_pk_*_f32, which costs more than two single-issue ops
     # beside MFMAs (MI355X_MICROARCH.md, per-instruction cycle constants)
     "attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
+    # attention.hip's flags, and the packed-fp32 target feature off: -fno-slp-vectorize stops the vectorizer, this
+    # stops instruction selection too, so no v_pk_{add,mul,fma}_f32 can appear beside the MFMAs (same reason as above;
+    # the kernels use no packed math, the generated code holds none either way)
+    "attention_wide.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
+                           "-packed-fp32-ops"],
 }
 
 

@@ -5,7 +5,8 @@
 //
 // Layout: Q [B, Nq, H, D], K/V [B, Nk, H, D] with explicit token / batch strides (the
 // to_q/to_k/to_v GEMM outputs are read in place: no head permute).  O likewise; LSE is
-// stored per (b, h, q) in the log2 domain.  Head dim Dv <= D (D in {64, 128}), zero padded.
+// stored per (b, h, q) in the log2 domain.  Head dim Dv <= D (D in {64, 128}), zero padded; 128 < Dv <= 160 is
+// dispatched to attention_wide.hip.
 //
 // Structure (per wave, 32 rows):
 //   forward / dQ : S^T = K Q^T  (keys in registers, query on the lane -> softmax row reduce is
@@ -26,6 +27,7 @@
 // single ops beside MFMAs), key masking only on the partial last tile, and the forward's O rescale skipped
 // when no lane's max grew.
 #include "common.h"
+#include "attention_args.h"
 
 #include <algorithm>
 #include <cstring>
@@ -35,16 +37,6 @@
 #include <utility>
 #include <type_traits>
 
-struct AttnArgs {
-  const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; float* lse;
-  const bf16_t* dout; const float* delta; bf16_t* dq; bf16_t* dk; bf16_t* dv; float* dk32; float* dv32;
-  long long ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;     // token strides (elements)
-  long long bsq, bsk, bsv, bso, bsdo, bsdq, bsdk, bsdv;     // batch strides (elements)
-  int B, H, Nq, Nk, Dv;
-  float scale;
-  int qsplit;
-  int xcd;   // (the header's reserved pad_; callers pass 0) set by the launchers: XCD-grouped block order
-};
 
 #define KT 64   // keys per staged tile (fwd / dQ)
 #define RESCALE_T 8.0f   // forward: lazy-max threshold (log2 units)
@@ -1021,6 +1013,9 @@ __global__ void attn_dkv_cast_kernel(AttnArgs a) {
   }
 }
 
+// heads of 129..160 columns: the one-block, split-stream kernels of attention_wide.hip (attention_args.h)
+static bool attn_wide(const AttnArgs& a) { return a.Dv > 128; }
+
 static bool getenv_flag(const char* name) {
   const char* v = std::getenv(name);
   return v && v[0] && v[0] != '0';
@@ -1030,7 +1025,7 @@ static bool getenv_flag(const char* name) {
 static bool fits31(int rows, long long ld) { return ((long long)rows * ld + 128) * 2 < 0x7fff0000LL; }
 
 static bool attn_ok(const AttnArgs& a) {
-  if (a.B <= 0 || a.H <= 0 || a.Nq <= 0 || a.Nk <= 0 || a.Dv <= 0 || a.Dv % 8 || a.Dv > 128) return false;
+  if (a.B <= 0 || a.H <= 0 || a.Nq <= 0 || a.Nk <= 0 || a.Dv <= 0 || a.Dv % 8 || a.Dv > 160) return false;
   const long long lds[] = {a.ldq, a.ldk, a.ldv, a.bsq, a.bsk, a.bsv};
   for (long long v : lds) if (v % 8) return false;
   if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) return false;
@@ -1081,6 +1076,7 @@ OTAMD_API int otamd_attn_fwd(const AttnArgs* in, hipStream_t stream) {
   if (!in || !attn_ok(*in) || !in->o || !in->lse) return OTAMD_EINVAL;
   AttnArgs a = *in;
   if (a.ldo % 8 || a.bso % 8 || ((uintptr_t)a.o & 15)) return OTAMD_EINVAL;   // 16-byte row stores
+  if (attn_wide(a)) return otamd_attn_wide_fwd(a, stream);
   dim3 grid((a.Nq + 127) / 128, a.H, a.B);
   if (a.Dv <= 64) launch(attn_fwd_kernel<64, 2>, grid, 2 * 2 * KT * 64 * 2, stream, a);   // 4 waves/SIMD: 279 vs 288 us
   else launch(attn_fwd_kernel<128, 2>, grid, 2 * 2 * KT * 128 * 2, stream, a);   // 369 vs 512 us (NS = 3), Flux 2381 tokens
@@ -1099,6 +1095,7 @@ static int attn_qsplit(const AttnArgs& a, bool cross) {
 
 static long long attn_ws_bytes(const AttnArgs* in, bool cross) {
   if (!in || in->B <= 0 || in->H <= 0 || in->Nq <= 0 || in->Nk <= 0 || in->Dv <= 0) return -1;
+  if (attn_wide(*in)) return otamd_attn_wide_ws_bytes(*in);
   const long long nrow = (long long)in->B * in->H * in->Nq;
   const long long nkv = (long long)in->B * in->Nk * in->H * in->Dv;
   const int qs = attn_qsplit(*in, cross);
@@ -1112,6 +1109,7 @@ OTAMD_API long long otamd_attn_bwd_ws_bytes(const AttnArgs* in) { return in ? at
 // otamd_attn_bwd_ex
 OTAMD_API long long otamd_attn_bwd_slab_bytes(const AttnArgs* in) {
   if (!in || in->B <= 0 || in->H <= 0 || in->Nq <= 0 || in->Nk <= 0 || in->Dv <= 0) return -1;
+  if (attn_wide(*in)) return 0;   // partials are combined inside the workgroup
   const int qs = attn_qsplit(*in, attn_cross_path(*in));
   return qs > 1 ? 2LL * qs * ((long long)in->B * in->Nk * in->H * in->Dv) * 4 : 0;
 }
@@ -1143,6 +1141,10 @@ static int attn_bwd_impl(const AttnArgs* in, float* ws, long long ws_bytes, floa
       (((uintptr_t)ws | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15))
     return OTAMD_EINVAL;   // 16-byte row stores
   if (((uintptr_t)a.dout & 15) || !fits31(a.Nq, a.lddo)) return OTAMD_EINVAL;
+  if (attn_wide(a)) {   // no slabs, no cast: dK / dV are complete on `stream`
+    if (ws_bytes < otamd_attn_wide_ws_bytes(a)) return OTAMD_EINVAL;
+    return otamd_attn_wide_bwd(a, ws, stream);
+  }
   const bool cross = attn_cross_path(a);
   const long long nrow = (long long)a.B * a.H * a.Nq;
   const long long nkv = (long long)a.B * a.Nk * a.H * a.Dv;

@@ -558,7 +558,7 @@ Tensor groupnorm_bwd(const Tensor& x, const Tensor& dy, const Tensor& gamma, int
   return dx;
 }
 
-// ---- flash attention (head dims <= 128): q [B, Nq, H*D] views, k / v [B, Nk, H*D] ----
+// ---- flash attention (head dims <= 160): q [B, Nq, H*D] views, k / v [B, Nk, H*D] ----
 std::pair<int64_t, int64_t> attn_view(const Tensor& t, int64_t heads) {
   req(t.dim() == 3 && is_bf16(t) && t.stride(2) == 1, "attention operand [B, N, H*D] bf16");
   req(t.size(2) % heads == 0, "channels must split into heads");
@@ -571,7 +571,7 @@ AttnArgs attn_args(const Tensor& q, const Tensor& k, const Tensor& v, int64_t he
   req(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "qkv");
   const int64_t B = q.size(0), Nq = q.size(1), Cq = q.size(2), Nk = k.size(1), D = Cq / heads;
   req(k.size(0) == B && v.size(0) == B && v.size(1) == Nk && k.size(2) == Cq && v.size(2) == Cq, "qkv");
-  req(D % 8 == 0 && D <= 128, "head dim must be a multiple of 8 and <= 128");
+  req(D % 8 == 0 && D <= 160, "head dim must be a multiple of 8 and <= 160");
   a.q = P(q); a.k = P(k); a.v = P(v);
   std::tie(a.ldq, a.bsq) = attn_view(q, heads);
   std::tie(a.ldk, a.bsk) = attn_view(k, heads);

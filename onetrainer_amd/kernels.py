@@ -1292,7 +1292,7 @@ def _attn_args(q, k, v, heads, scale):
     Nk = k.shape[1]
     D = Cq // heads
     _req(k.shape[0] == B and v.shape[0] == B and v.shape[1] == Nk and k.shape[2] == Cq and v.shape[2] == Cq, "qkv")
-    _req(D % 8 == 0 and D <= 128, "head dim must be a multiple of 8 and <= 128")
+    _req(D % 8 == 0 and D <= FLASH_MAX_D, "head dim must be a multiple of 8 and <= 160")
     a.q, a.k, a.v = _p(q), _p(k), _p(v)
     a.ldq, a.bsq = _attn_view(q, heads)
     a.ldk, a.bsk = _attn_view(k, heads)
@@ -1302,7 +1302,18 @@ def _attn_args(q, k, v, heads, scale):
     return a
 
 
-FLASH_MAX_D = 128
+FLASH_MAX_D = 160
+# Heads of 129..160 columns (csrc/attention_wide.hip) take the flash kernels up to this many scores B H Nq Nk.
+# Measured forward + backward at the SD 1.5 deep-level shapes, batch 4 and 16 ("160-wide flash attention"):
+# every shape of up to 2.5 M scores is faster on the flash kernels (16 x 8 x 256 x 77, 4 x 8 x 1024 x 77 and all
+# smaller), every shape from 8.4 M scores on is slower (16 x 8 x 256 x 256 and all larger): what decides is the amount
+# of work, not the key count.  Nothing was measured in between; the bound is 2^22, near the geometric mean of the two.
+WIDE_FLASH_MAX_SCORES = 1 << 22
+
+
+def _flash_route(q, k, heads) -> bool:
+    D = q.shape[-1] // heads
+    return D <= 128 or (D <= FLASH_MAX_D and q.shape[0] * heads * q.shape[1] * k.shape[1] <= WIDE_FLASH_MAX_SCORES)
 
 
 def _span_ok(t: torch.Tensor, last_elem: int) -> bool:
@@ -1419,8 +1430,8 @@ def attn_mat_bwd(q, k, v, P, dout, heads, scale=None, dq=None, dk=None, dv=None)
 
 def attn_fwd(q, k, v, heads, scale=None, out=None):
     """softmax(q k^T * scale) v per head; returns (o [B,Nq,H*D] bf16, aux): aux is the flash
-    kernels' lse [B,H,Nq] (log2 domain) for head dims <= 128, else the materialized P."""
-    if q.shape[-1] // heads > FLASH_MAX_D:
+    kernels' lse [B,H,Nq] (log2 domain) on the flash route (_flash_route), else the materialized P."""
+    if not _flash_route(q, k, heads):
         return attn_mat_fwd(q, k, v, heads, scale, out)
     h = _host()
     if h is not None:
@@ -1440,7 +1451,7 @@ def attn_bwd(q, k, v, o, lse, dout, heads, scale=None, dq=None, dk=None, dv=None
     (otamd_attn_bwd_ex); dk / dv are then written on that stream, after an event on the current one -- for callers
     whose dK / dV feed only work queued on cast_stream.  The slabs come from the caching allocator and are
     record_stream()ed, as are dk / dv."""
-    if q.shape[-1] // heads > FLASH_MAX_D:
+    if not _flash_route(q, k, heads):
         return attn_mat_bwd(q, k, v, lse, dout, heads, scale, dq, dk, dv)
     h = _host()
     if h is not None and cast_stream is None:

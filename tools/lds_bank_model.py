@@ -79,6 +79,12 @@ def main():
             best = min((row_cost(xor_layout(D, parity_fn(m)), D) + tr_cost(xor_layout(D, parity_fn(m)), D), m)
                        for m in itertools.product(range(32), repeat=(nch - 1).bit_length()))
             print("  best XOR layout found: cost", best[0], "masks", best[1])
+    # attention_wide.hip: 320-byte rows (20 chunks).  Only the low two chunk bits are XORed, so the chunk count stays 20.
+    D = 160
+    print(f"D = {D}: conflict-free costs row {4 * (D // 16)}, transposed {2 * 4 * (D // 32)}")
+    for name, f in (("unswizzled", lambda r: 0), ("row-only (ch ^ (r & 3))", lambda r: r & 3),
+                    ("wide (ch ^ ((r >> 2) & 3))", lambda r: (r >> 2) & 3)):
+        print(f"  {name}:", row_cost(xor_layout(D, f), D), tr_cost(xor_layout(D, f), D))
 
 
 if __name__ == "__main__":
