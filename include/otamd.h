@@ -230,6 +230,13 @@ long long otamd_attn_bwd_slab_bytes(const AttnArgs* in);
 int otamd_attn_bwd_ex(const AttnArgs* in, float* ws, long long ws_bytes, float* slabs, long long slab_bytes,
                       hipStream_t stream, hipStream_t cast_stream);
 
+/* replaces: F.scaled_dot_product_attention in diffusers Attention of the AutoencoderKL mid block (one 512-wide head;
+   encoder for latent caching, decoder for samples): flash forward for heads wider than 160, csrc/attention_vae.hip.
+   Forward only, no lse (in->lse and the backward fields are ignored).  OTAMD_EINVAL: Dv is not an instantiated width
+   (512), a stride not a multiple of 8, a pointer not 16-byte aligned, Nq / Nk / B / H < 1, scale <= 0, K / V rows
+   beyond the 31-bit DMA offsets */
+int otamd_attn_xwide_fwd(const AttnArgs* in, hipStream_t stream);
+
 /* replaces: ABI check */
 int otamd_attn_args_size(void);
 

@@ -227,6 +227,7 @@ SIGNATURES: dict[str, list] = {
     # attention.hip
     "otamd_attn_args_size": [],
     "otamd_attn_fwd": [C.POINTER(AttnArgs), VP],
+    "otamd_attn_xwide_fwd": [C.POINTER(AttnArgs), VP],
     "otamd_attn_bwd": [C.POINTER(AttnArgs), VP, LL, VP],
     "otamd_attn_bwd_ws_bytes": [C.POINTER(AttnArgs)],
     "otamd_attn_bwd_slab_bytes": [C.POINTER(AttnArgs)],

@@ -48,6 +48,10 @@ EXTRA = {
     # the kernels use no packed math, the generated code holds none either way)
     "attention_wide.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang",
                            "-packed-fp32-ops"],
+    # attention.hip's flags, and MFMA results selected in VGPR form: a one-wave-per-SIMD kernel otherwise gets every
+    # accumulator in AGPRs, and O^T (256) plus S^T (16) exceed the 256 there; with the VGPR form the allocator splits
+    # O^T / Q over both files by itself (no spills; DESIGN.md, "Flash attention for the VAE's 512-wide head")
+    "attention_vae.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

@@ -1311,6 +1311,17 @@ FLASH_MAX_D = 160
 WIDE_FLASH_MAX_SCORES = 1 << 22
 
 
+# Head widths of the forward-only flash kernel for heads wider than FLASH_MAX_D (csrc/attention_vae.hip).
+XWIDE_DIMS = (512,)
+# The AutoencoderKL mid block's single 512-wide head (module/vae.py) takes that kernel from this many tokens on; below
+# it keeps the materialized path.  Measured forward alone at D = 512, N in {1024, 4096, 16384}, B in {1, 4}, the two
+# paths interleaved ("Flash attention for the VAE's 512-wide head"): at 1024 and 4096 tokens the flash
+# kernel is slower at both batch sizes (128-query workgroups: 8 and 32 per image on 256 CUs), at 16384 (a 1024^2
+# image) it is faster at both (1.16x at batch 1, 2.3x at batch 4).  The value is the smallest measured N from which it
+# is no slower at both batch sizes; nothing was measured between 4096 and 16384.
+VAE_FLASH_MIN_TOKENS = 16384
+
+
 def _flash_route(q, k, heads) -> bool:
     D = q.shape[-1] // heads
     return D <= 128 or (D <= FLASH_MAX_D and q.shape[0] * heads * q.shape[1] * k.shape[1] <= WIDE_FLASH_MAX_SCORES)
@@ -1397,6 +1408,36 @@ def attn_mat_fwd(q, k, v, heads, scale=None, out=None):
     gemm_batched(P, Nkp, OPM_K, vp, vp.stride(1), OPM_MN, out, out.stride(1), Nq, D, Nkp, B * H, H,
                  (H * Nq * Nkp, Nq * Nkp), (vp.stride(0), D), (out.stride(0), D))
     return out, P
+
+
+def attn_xwide_fwd(q, k, v, heads, scale=None, out=None):
+    """Flash attention forward for heads wider than FLASH_MAX_D (the widths in XWIDE_DIMS: the VAE's 512-wide single
+    head): o = softmax(scale q k^T) v with no [Nq, Nk] buffer.  Forward only; returns o [B, Nq, H*D] bf16."""
+    _req(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention operand [B, N, H*D] bf16")
+    B, Nq, Cq = q.shape
+    Nk = k.shape[1]
+    _req(heads >= 1 and Cq % heads == 0, "channels must split into heads")
+    D = Cq // heads
+    _req(D in XWIDE_DIMS, f"attn_xwide_fwd: head dim must be one of {XWIDE_DIMS} (heads up to {FLASH_MAX_D} columns: "
+         "attn_fwd)")
+    _req(k.shape[0] == B and v.shape[0] == B and v.shape[1] == Nk and k.shape[2] == Cq and v.shape[2] == Cq, "qkv")
+    _req(Nq >= 1 and Nk >= 1 and B >= 1, "attn_xwide_fwd: empty operand")
+    if out is None:
+        out = torch.empty(q.shape, dtype=BF16, device=q.device)
+    _req(out.shape == q.shape, "attn_xwide_fwd: out must have q's shape")
+    a = _lib.AttnArgs()
+    a.q, a.k, a.v, a.o = _p(q), _p(k), _p(v), _p(out)
+    a.ldq, a.bsq = _attn_view(q, heads)
+    a.ldk, a.bsk = _attn_view(k, heads)
+    a.ldv, a.bsv = _attn_view(v, heads)
+    a.ldo, a.bso = _attn_view(out, heads)
+    _req(_aligned(q) and _aligned(k) and _aligned(v) and _aligned(out)
+         and all(s % 8 == 0 for s in (a.ldq, a.ldk, a.ldv, a.ldo, a.bsq, a.bsk, a.bsv, a.bso)),
+         "attn_xwide_fwd: 16-byte aligned operands, strides in multiples of 8")
+    a.B, a.H, a.Nq, a.Nk, a.Dv = B, heads, Nq, Nk, D
+    a.scale = scale if scale is not None else D ** -0.5
+    check(lib().otamd_attn_xwide_fwd(C.byref(a), stream_handle()), "otamd_attn_xwide_fwd")
+    return out
 
 
 def attn_mat_bwd(q, k, v, P, dout, heads, scale=None, dq=None, dk=None, dv=None):

@@ -17,8 +17,10 @@ FLUX.1's AutoencoderKL (flux_vae_config, FluxBaseDataLoader.py:70-71 + BaseFluxS
 encoder with 16 latent channels (conv_out 512->32) and no quant_conv: mean = conv_out channels [0, 16); the
 setup applies (latent - shift_factor) * scaling_factor.
 Kernels: implicit-GEMM convs (stride 2 + one-sided zero padding through the conv gather's range
-check), GroupNorm(+SiLU), fused q|k|v Linear, the materialized single-head attention (512-wide
-head: batched MFMA GEMMs + row softmax), and the quant_conv mean rows as one fp32-out GEMM.
+check), GroupNorm(+SiLU), fused q|k|v Linear, the single-head attention of the 512-wide mid block -- from
+kernels.VAE_FLASH_MIN_TOKENS tokens on the forward-only flash kernel (csrc/attention_vae.hip: no [N, N] score
+buffers, 6 B N^2 bytes of transients gone), below it the materialized path (batched MFMA GEMMs + row softmax) --
+and the quant_conv mean rows as one fp32-out GEMM.
 
 AutoencoderKLDecoder (below) is the decoder half for the training samples (modelSampler/): post_quant_conv, conv_in,
 the same mid block, UpDecoderBlock2D x n (layers_per_block + 1 resnets, nearest-2x Upsample2D through
@@ -199,10 +201,14 @@ class _VAEBlocks:
         wqkv = self.store.view([f"{p}.to_{c}.weight" for c in "qkv"], (3 * C, C))
         bqkv = self.store.view([f"{p}.to_{c}.bias" for c in "qkv"], (3 * C,))
         qkv = K.linear(h.view(-1, C), wqkv, bias=bqkv).view(N, H * W_, 3 * C)
-        # the single head keeps the materialized path at every width above 128 (the frozen-network parity bounds
-        # were measured on it); the 160-wide flash kernels serve the UNet's heads
-        attn = K.attn_mat_fwd if C > 128 else K.attn_fwd
-        o, _ = attn(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], 1)
+        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+        if C > K.FLASH_MAX_D and H * W_ >= K.VAE_FLASH_MIN_TOKENS:
+            # the 512-wide head from VAE_FLASH_MIN_TOKENS tokens on: flash forward, no [N, N] score buffers
+            o = K.attn_xwide_fwd(q, k, v, 1)
+        else:
+            # below it the single head keeps the materialized path at every width above 128 (the frozen-network
+            # parity bounds were measured on it); the 160-wide flash kernels serve the UNet's heads
+            o, _ = (K.attn_mat_fwd if C > 128 else K.attn_fwd)(q, k, v, 1)
         out = K.linear(o.view(-1, C), self.W(p + ".to_out.0.weight"), bias=self.W(p + ".to_out.0.bias"),
                        residual=x.view(-1, C))
         return out.view(N, H, W_, C)
