@@ -17,10 +17,7 @@
 // Staging: every streamed tile (K/V for fwd and dQ, Q/dO and the {lse, delta} pairs for dK/dV)
 // goes HBM/L2 -> LDS by LDS-DMA (buffer_load ... lds) into an NS-deep ring, the swizzles applied
 // on the source address; one s_barrier per tile (RAW for tile t, WAR for the stage refilled
-// with tile t+NS-1).  That barrier is BARRIER_LDS: gfx950's s_barrier does not wait for a wave's
-// outstanding ds_reads, and the compiler sinks the last MFMA of a tile (with the lgkmcnt wait for
-// its operand reads) below a raw s_barrier -- another wave's refill DMA then raced the reads it
-// had issued (dQ run-to-run differences under LDS contention from co-resident kernels, round 6).
+// with tile t+NS-1).  That barrier is BARRIER_LDS; its rule and the LDS-DMA's are in mfma_prims.h.
 // Out-of-range rows / padded head columns are zero-filled by the descriptor range check or an
 // invalid offset.
 // Softmax VALU is kept under the MFMA time: single-issue fp32 math (no v_pk_*: they cost more than two
@@ -28,59 +25,30 @@
 // when no lane's max grew.
 #include "common.h"
 #include "attention_args.h"
+#include "mfma_prims.h"
 
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
-#include <mutex>
-#include <unordered_set>
 #include <utility>
 #include <type_traits>
 
 
 #define KT 64   // keys per staged tile (fwd / dQ)
-#define RESCALE_T 8.0f   // forward: lazy-max threshold (log2 units)
-#define OFF_INVALID 0x80000000u
-static constexpr float LOG2E = 1.4426950408889634f;
 
-typedef __attribute__((address_space(3))) short4v lds_s4;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-#define MEMBAR() asm volatile("" ::: "memory")
-#define BARRIER()                 \
-  do {                            \
-    MEMBAR();                     \
-    __builtin_amdgcn_s_barrier(); \
-    MEMBAR();                     \
+// This file's BARRIER_LDS keeps a compiler fence in front of s_barrier as well (the rule itself: mfma_prims.h).  With
+// the shared form the scheduler moves one scalar op across the lgkmcnt wait in five of these kernels; the kernels
+// are kept as they were measured.
+#undef BARRIER_LDS
+#define BARRIER_LDS() \
+  do {                \
+    WAIT_LDS();       \
+    BARRIER();        \
   } while (0)
 
-// publishes this wave's ds_write results: s_barrier alone does not wait for them (cdna_hip_programming.md §5)
-#define BARRIER_LDS()                                     \
-  do {                                                    \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
-    BARRIER();                                            \
-  } while (0)
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// LDS-DMA, 16 / 4 bytes per lane (1 KiB / 256 B per wave instruction).  Inline asm so the
-// compiler's waitcnt pass does not drain vmcnt in front of ds_reads of other stages.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds, unsigned off) {
-  const unsigned m0 = (unsigned)(size_t)(lds_void_t*)lds;
-  asm volatile("buffer_load_dwordx4 %1, %2, 0 offen lds" ::"{m0}"(m0), "v"(off), "s"(rs) : "memory");
-}
-__device__ __forceinline__ void dma4(__amdgpu_buffer_rsrc_t rs, char* lds, unsigned off) {
-  const unsigned m0 = (unsigned)(size_t)(lds_void_t*)lds;
-  asm volatile("buffer_load_dword %1, %2, 0 offen lds" ::"{m0}"(m0), "v"(off), "s"(rs) : "memory");
-}
 // make the compiler drain its own loads of x here (before any DMA it cannot see is in flight)
 template <typename T>
 __device__ __forceinline__ void consume(const T& x) { asm volatile("" ::"v"(x)); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, long long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
 
 // Workgroup order (cdna_hip_programming.md T1): the hardware deals workgroup i (x fastest) to XCD i % 8, so the
 // blocks of one (batch, head) -- which all stream that head's K / V (forward, dQ) or Q / dO (dK/dV) tiles --
@@ -122,10 +90,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* img, int row0, int s, int 
   const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3, h = lane >> 5;
   const int r = row0 + 16 * s + 4 * h + q;
   const int col = col0 + 16 * (G & 1) + 4 * p;
-  const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(img + tr_off<D>(r, col)));
-  const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(img + tr_off<D>(r + 8, col)));
-  short8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return tr16_pair(img, tr_off<D>(r, col), tr_off<D>(r + 8, col));
 }
 
 // Dual-use image (cdna_hip_programming.md T10, "one image for row reads AND transposed reads"): [rows][D] bf16,
@@ -165,10 +130,7 @@ template <int D> struct DualOffs {
   // tr_frag's operand (rows row0 + 16 s ..) of column block dt
   __device__ __forceinline__ bf16x8 trf(const char* img, int row0, int s, int dt) const {
     const char* base = img + (row0 + 16 * s) * (D * 2);
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + tr[dt][0]));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + tr[dt][1]));
-    short8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
+    return tr16_pair(base, tr[dt][0], tr[dt][1]);
   }
 };
 
@@ -179,31 +141,6 @@ __device__ __forceinline__ uint2 split3_bf16(float x) {
   const bf16_t t1 = f2bf(r1);
   const bf16_t t2 = f2bf(r1 - bf2f(t1));
   return make_uint2((uint32_t)t0 | ((uint32_t)t1 << 16), (uint32_t)t2);
-}
-
-__device__ __forceinline__ bf16x8 pack_acc(const float16v& a, int s) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)a[8 * s + j];
-  return r;
-}
-
-__device__ __forceinline__ float16v mfma32(const bf16x8& a, const bf16x8& b, const float16v& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float16v zero16() {
-  float16v z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-// row (in the 32-row accumulator tile) held by register i of this lane
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-// value of x in lane l ^ 32 (one permlane32 swap + select)
-__device__ __forceinline__ float xor32(float x) {
-  const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((threadIdx.x & 32) ? s[0] : s[1]);
 }
 
 // 32 rows x 32 columns of fp32 accumulators (one 32x32 MFMA tile; lane (r, h) holds columns
@@ -1021,15 +958,12 @@ static bool getenv_flag(const char* name) {
   return v && v[0] && v[0] != '0';
 }
 
-// the per-(batch, head) DMA descriptors address rows with 31-bit byte offsets
-static bool fits31(int rows, long long ld) { return ((long long)rows * ld + 128) * 2 < 0x7fff0000LL; }
-
 static bool attn_ok(const AttnArgs& a) {
   if (a.B <= 0 || a.H <= 0 || a.Nq <= 0 || a.Nk <= 0 || a.Dv <= 0 || a.Dv % 8 || a.Dv > 160) return false;
   const long long lds[] = {a.ldq, a.ldk, a.ldv, a.bsq, a.bsk, a.bsv};
   for (long long v : lds) if (v % 8) return false;
   if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) return false;
-  if (!fits31(a.Nq, a.ldq) || !fits31(a.Nk, a.ldk) || !fits31(a.Nk, a.ldv)) return false;
+  if (!fits31(a.Nq, a.ldq, 128) || !fits31(a.Nk, a.ldk, 128) || !fits31(a.Nk, a.ldv, 128)) return false;
   return true;
 }
 
@@ -1042,17 +976,9 @@ static int xcd_order() {
   return on;
 }
 
-template <typename K>
-static void launch(K kern, dim3 grid, int lds, hipStream_t s, AttnArgs a) {
+static void launch(void (*kern)(AttnArgs), dim3 grid, int lds, hipStream_t s, AttnArgs a) {
   a.xcd = xcd_order();
-  {   // LDS opt-in once per kernel instance (its LDS size is fixed by the template)
-    static std::mutex mu;
-    static std::unordered_set<const void*> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.insert((const void*)kern).second)
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+  attn_launch(kern, grid, lds, s, a);
 }
 
 // one-pass cross-attention backward (attn_bwd_cross_kernel): short key sets at head dim <= 64
@@ -1140,7 +1066,7 @@ static int attn_bwd_impl(const AttnArgs* in, float* ws, long long ws_bytes, floa
   if (a.lddo % 8 || a.bsdo % 8 || a.lddq % 8 || a.lddk % 8 || a.lddv % 8 || a.bsdq % 8 || a.bsdk % 8 || a.bsdv % 8 ||
       (((uintptr_t)ws | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15))
     return OTAMD_EINVAL;   // 16-byte row stores
-  if (((uintptr_t)a.dout & 15) || !fits31(a.Nq, a.lddo)) return OTAMD_EINVAL;
+  if (((uintptr_t)a.dout & 15) || !fits31(a.Nq, a.lddo, 128)) return OTAMD_EINVAL;
   if (attn_wide(a)) {   // no slabs, no cast: dK / dV are complete on `stream`
     if (ws_bytes < otamd_attn_wide_ws_bytes(a)) return OTAMD_EINVAL;
     return otamd_attn_wide_bwd(a, ws, stream);

@@ -30,8 +30,9 @@
 // LDS (128 KiB, dynamic: needs the opt-in attribute): K ring of two [32 x 512] bf16 images (32 KiB each) and a V
 // ring of two.  Tile j + 1 is staged by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB = one key row per wave
 // instruction, each wave 8 rows of K and 8 of V) right after the barrier that opens tile j, so it has a whole tile of
-// MFMAs (64 x 32 cycles) to land; one barrier per tile: every wave's pieces of tile j have landed (vmcnt(0) before
-// it) and every wave's reads of tile j - 1 have retired (lgkmcnt(0) before it) -- the slot the refill goes to.
+// MFMAs (64 x 32 cycles) to land; one barrier per tile (BARRIER_LDS after vmcnt(0); its rule, the LDS-DMA and the
+// MFMA helpers: mfma_prims.h): every wave's pieces of tile j have landed and every wave's reads of tile j - 1, the
+// slot the refill goes to, have retired.
 // Rows past Nk are zero-filled through an invalid buffer offset (V: 0 x garbage must not reach O) and masked to -inf.
 //   Reads: K by rows (ds_read_b128: lane (r, h) <- key r, columns 16 s + 8 h ..), V transposed
 //   (ds_read_b64_tr_b16), each 1 KiB per wave per MFMA.  LDS bytes per MFMA: 1024 per 32 cycles and wave, 128 B/clk
@@ -55,6 +56,7 @@
 // queries lie past Nq (Nq % 128 <= 96) still runs its MFMAs.
 #include "common.h"
 #include "attention_args.h"
+#include "mfma_prims.h"
 
 #include <cmath>
 
@@ -66,55 +68,7 @@ constexpr int KT = 32;                // keys per tile
 constexpr int RB = DH * 2;            // row bytes = one DMA piece
 constexpr int IMG = KT * RB;          // one [32 x 512] bf16 image (32 KiB)
 constexpr int XW_LDS = 4 * IMG;       // K ring of two, V ring of two
-constexpr float RESCALE_T = 8.0f;     // lazy-max threshold (log2 units)
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr float LOG2E = 1.4426950408889634f;
 static_assert(RB == 1024, "one key row = one 1 KiB LDS-DMA piece (64 lanes x 16 bytes)");
-
-typedef __attribute__((address_space(3))) short4v lds_s4;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-#define MEMBAR() asm volatile("" ::: "memory")
-#define WAIT_LDS() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define WAIT_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-// s_barrier waits for no outstanding ds_read of this wave (attention.hip): drain them first
-#define BARRIER_LDS()             \
-  do {                            \
-    WAIT_LDS();                   \
-    __builtin_amdgcn_s_barrier(); \
-    MEMBAR();                     \
-  } while (0)
-
-// 64 lanes x 16 bytes from rs[voff + soff] to lds[16 lane ..]; the range check sees voff alone
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds, unsigned voff, unsigned soff) {
-  const unsigned m0 = (unsigned)(size_t)(lds_void_t*)lds;
-  asm volatile("buffer_load_dwordx4 %1, %2, %3 offen lds" ::"{m0}"(m0), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, long long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float16v mfma32(const bf16x8& a, const bf16x8& b, const float16v& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float16v zero16() {
-  float16v z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-// accumulator registers 8s .. 8s+7 as the next MFMA's B operand (k = the accumulator's row)
-__device__ __forceinline__ bf16x8 pack_acc(const float16v& a, int s) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)a[8 * s + j];
-  return r;
-}
-// row (of the 32-row accumulator tile) held by register i of lane half h
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-__device__ __forceinline__ float xor32(float x) {
-  const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((threadIdx.x & 32) ? s[0] : s[1]);
-}
 
 // chunk swizzle of row r (low four chunk bits)
 __device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
@@ -142,10 +96,7 @@ struct XImg {
   __device__ __forceinline__ bf16x8 trf(const char* img, int s, int dt) const {
     const char* base = img + 16 * RB * s + 256 * (dt >> 2);
     const int x = (dt & 3) << 6;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + (tro[0] ^ x)));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + (tro[1] ^ x)));
-    short8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
+    return tr16_pair(base, tro[0] ^ x, tro[1] ^ x);
   }
 };
 
@@ -282,9 +233,6 @@ __global__ void __launch_bounds__(256, 1) attn_xwide_fwd_kernel(AttnArgs a) {
   }
 }
 
-// the per-(batch, head) DMA descriptors address rows with 31-bit byte offsets
-bool fits31(int rows, long long ld) { return ((long long)rows * ld + DH) * 2 < 0x7fff0000LL; }
-
 }   // namespace
 
 OTAMD_API int otamd_attn_xwide_fwd(const AttnArgs* in, hipStream_t stream) {
@@ -300,13 +248,8 @@ OTAMD_API int otamd_attn_xwide_fwd(const AttnArgs* in, hipStream_t stream) {
       a.ldo < (long long)a.H * DH)
     return OTAMD_EINVAL;
   if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.o) & 15) return OTAMD_EINVAL;
-  if (!fits31(a.Nk, a.ldk) || !fits31(a.Nk, a.ldv)) return OTAMD_EINVAL;
-  static const bool once = [] {   // LDS opt-in above 64 KiB
-    (void)hipFuncSetAttribute((const void*)attn_xwide_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, XW_LDS);
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(attn_xwide_fwd_kernel, dim3((a.Nq + QT - 1) / QT, a.H, a.B), dim3(256), XW_LDS, stream, a);
+  if (!fits31(a.Nk, a.ldk, DH) || !fits31(a.Nk, a.ldv, DH)) return OTAMD_EINVAL;
+  attn_launch(attn_xwide_fwd_kernel, dim3((a.Nq + QT - 1) / QT, a.H, a.B), XW_LDS, stream, a);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

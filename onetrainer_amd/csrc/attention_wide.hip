@@ -21,9 +21,9 @@
 //   4 x 8 x 576 x 576 and larger), so the Python layer routes 160-wide heads to these kernels up to 2^22 scores.
 //
 // Data movement.  No tile is shared between waves, so there is no workgroup barrier in any tile loop: a wave
-// synchronises only with its own counters (s_waitcnt vmcnt / lgkmcnt), which also rules out the round-6 race class
-// (another wave's refill DMA against outstanding ds_reads); the refill of a wave's own slot is issued after
-// s_waitcnt lgkmcnt(0).  The two barriers of the final combine are BARRIER_LDS.
+// synchronises only with its own counters (s_waitcnt vmcnt / lgkmcnt); the refill of a wave's own slot is issued
+// after s_waitcnt lgkmcnt(0).  The barriers of the final combine are BARRIER_LDS (its rule and the LDS-DMA's:
+// mfma_prims.h, which also holds the MFMA helpers).
 //   MFMA row operands (A of S^T = K Q^T, dP^T = V dO^T, S = Q K^T, dP = dO V^T) need no transposition: they are loaded
 //   from HBM/L2 straight into registers, 16 bytes per lane, one sub-tile ahead (the registers are the double buffer).
 //   Transposed operands (V^T for O^T, K^T for dQ^T, dO^T / Q^T for dV^T / dK^T) go HBM/L2 -> LDS by LDS-DMA into the
@@ -57,7 +57,7 @@
 // sub-tile and spills 5 VGPRs (24 bytes of scratch per lane) at 256 + 256 registers.
 #include "common.h"
 #include "attention_args.h"
-
+#include "mfma_prims.h"
 
 namespace {
 
@@ -68,53 +68,6 @@ constexpr int NPIECE = IMG / 1024;    // DMA pieces per image
 constexpr int REGION = 2 * IMG;       // a wave's private LDS (20 KiB) = its fp32 partial [160][32]
 constexpr int SHARED = 4 * REGION;    // after the four regions: the forward's {m, l} table / dK/dV's K and V images
 constexpr int WIDE_LDS = SHARED + 2 * IMG;   // 100 KiB
-constexpr float RESCALE_T = 8.0f;     // forward: lazy-max threshold (log2 units)
-constexpr unsigned OFF_INVALID = 0x80000000u;
-constexpr float LOG2E = 1.4426950408889634f;
-
-typedef __attribute__((address_space(3))) short4v lds_s4;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-#define MEMBAR() asm volatile("" ::: "memory")
-#define WAIT_LDS() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define WAIT_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-// s_barrier waits for no outstanding ds_read / ds_write of this wave (attention.hip): drain them first
-#define BARRIER_LDS()             \
-  do {                            \
-    WAIT_LDS();                   \
-    __builtin_amdgcn_s_barrier(); \
-    MEMBAR();                     \
-  } while (0)
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds, unsigned off) {
-  const unsigned m0 = (unsigned)(size_t)(lds_void_t*)lds;
-  asm volatile("buffer_load_dwordx4 %1, %2, 0 offen lds" ::"{m0}"(m0), "v"(off), "s"(rs) : "memory");
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, long long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float16v mfma32(const bf16x8& a, const bf16x8& b, const float16v& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float16v zero16() {
-  float16v z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-// accumulator registers 8s .. 8s+7 as the next MFMA's B operand (k = the accumulator's row)
-__device__ __forceinline__ bf16x8 pack_acc(const float16v& a, int s) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)a[8 * s + j];
-  return r;
-}
-// row (of the 32-row accumulator tile) held by register i of lane half h
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-__device__ __forceinline__ float xor32(float x) {
-  const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((threadIdx.x & 32) ? s[0] : s[1]);
-}
 
 __device__ __forceinline__ int wsw(int r) { return (r >> 2) & 3; }
 
@@ -167,10 +120,7 @@ struct WideImg {
   // (j & 3), column 32 dt + (lane & 31)
   __device__ __forceinline__ bf16x8 trf(const char* img, int s, int dt) const {
     const char* base = img + 16 * RB * s + 64 * dt;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + tro[0]));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(base + tro[1]));
-    short8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
+    return tr16_pair(base, tro[0], tro[1]);
   }
 };
 
@@ -536,21 +486,11 @@ __global__ void __launch_bounds__(256, 1) attn_wide_dkv_kernel(AttnArgs a) {
   combine(smem, one, 1.f, a.dv + b * a.bsdv + hh * a.Dv, a.lddv, k0, a.Nk, a.Dv);
 }
 
-template <typename K>
-void launch_wide(K kern, dim3 grid, hipStream_t s, const AttnArgs& a) {
-  static const bool once = [&] {   // LDS opt-in, once per kernel instance
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(kern, grid, dim3(256), WIDE_LDS, s, a);
-}
-
 }   // namespace
 
 // Called by otamd_attn_fwd / otamd_attn_bwd (attention.hip) with checked arguments, 128 < Dv <= 160.
 int otamd_attn_wide_fwd(const AttnArgs& a, hipStream_t stream) {
-  launch_wide(attn_wide_fwd_kernel, dim3((a.Nq + 31) / 32, a.H, a.B), stream, a);
+  attn_launch(attn_wide_fwd_kernel, dim3((a.Nq + 31) / 32, a.H, a.B), WIDE_LDS, stream, a);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }
@@ -561,8 +501,8 @@ long long otamd_attn_wide_ws_bytes(const AttnArgs& a) { return (long long)a.B * 
 int otamd_attn_wide_bwd(const AttnArgs& in, float* ws, hipStream_t stream) {
   AttnArgs a = in;
   a.delta = ws;
-  launch_wide(attn_wide_dq_kernel, dim3((a.Nq + 31) / 32, a.H, a.B), stream, a);
-  launch_wide(attn_wide_dkv_kernel, dim3((a.Nk + 31) / 32, a.H, a.B), stream, a);
+  attn_launch(attn_wide_dq_kernel, dim3((a.Nq + 31) / 32, a.H, a.B), WIDE_LDS, stream, a);
+  attn_launch(attn_wide_dkv_kernel, dim3((a.Nk + 31) / 32, a.H, a.B), WIDE_LDS, stream, a);
   OTAMD_CHECK_LAUNCH();
   return OTAMD_OK;
 }

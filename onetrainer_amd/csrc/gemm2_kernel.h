@@ -16,6 +16,7 @@
 #pragma once
 #include "gemm.h"
 #include "gemm2_stage.h"
+#include "mfma_prims.h"   // BARRIER, wait_vmcnt<N>, dma16 (the LDS-DMA and its ordering rule), rsrc, tr16_pair
 
 // Timing ablations of the K loop (tools/gemm_ablate.sh builds them as separate libraries; results are garbage):
 //   1 = no DMA after the prologue, 2 = no MFMA (fragments kept live), 3 = no fragment reads after the prologue,
@@ -23,32 +24,6 @@
 #ifndef OTAMD_GEMM_ABL
 #define OTAMD_GEMM_ABL 0
 #endif
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(3))) short4v lds_s4_t;
-
-#define MEMBAR() asm volatile("" ::: "memory")
-#define BARRIER()                      \
-  do {                                 \
-    MEMBAR();                          \
-    __builtin_amdgcn_s_barrier();      \
-    MEMBAR();                          \
-  } while (0)
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// One 16-byte-per-lane LDS-DMA (1 KiB per wave). Issued as inline asm on purpose: the compiler's
-// waitcnt pass cannot prove that a later ds_read of the OTHER LDS stage does not alias an
-// in-flight builtin LDS-DMA and would drain vmcnt in front of it, serialising the pipeline.
-// Ordering is owned here: every read of a stage follows wait_vmcnt<> + BARRIER on its DMA.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds, unsigned off) {
-  const unsigned m0 = (unsigned)(size_t)(lds_void_t*)lds;
-  asm volatile("buffer_load_dwordx4 %1, %2, 0 offen lds" ::"{m0}"(m0), "v"(off), "s"(rs) : "memory");
-}
 
 // One operand tile's DMA: the index decode of gemm2_stage.h (StageIndex) plus the issue of its pieces.  The conv
 // gathers carry their decode from K-step to K-step (offsets_step: no division in the K loop), so their tiles must be
@@ -100,10 +75,7 @@ __device__ __forceinline__ bf16x8 frag_mn2(const char* img, int mnb, int kb) {
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   const int k0 = kb + 8 * g + q;
   const int col = mnb + 4 * p;
-  const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(img + mn_off<RB>(k0, col)));
-  const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(img + mn_off<RB>(k0 + 4, col)));
-  short8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return tr16_pair(img, mn_off<RB>(k0, col), mn_off<RB>(k0 + 4, col));
 }
 
 // NW = 8: 2 waves/SIMD (<= 256 VGPRs), wave tiles 128x64 / 64x64.  NW = 4: 1 wave/SIMD (512-entry
@@ -181,8 +153,7 @@ __global__ void __launch_bounds__(NW * 64, (LDR == 0 && NS == 2 && BM == 128 && 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
 
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)args.A, (short)0, (int)a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)args.B, (short)0, (int)b_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = rsrc(args.A, a_bytes), rb = rsrc(args.B, b_bytes);
   // closed-form gathers, from profiles/conv_index_static.md: the carried state cost conv fwd 256x160 its third wave
   // (168 -> 170 VGPRs), wgrad 128x64 its eighth (64 -> 65) and the 128x160 colsum wgrad 20 more bytes of scratch
   constexpr bool conv_inc_a = !(AM == OPM_CONV_FWD && BM == 256 && BN == 160 && !SEG2 && !LD);
@@ -199,8 +170,8 @@ __global__ void __launch_bounds__(NW * 64, (LDR == 0 && NS == 2 && BM == 128 && 
   Stage<B2M, SEG2 ? BN : 64 * NW / 8, NW> sb2;
   __amdgpu_buffer_rsrc_t ra2 = ra, rb2 = rb;
   if constexpr (SEG2) {
-    ra2 = __builtin_amdgcn_make_buffer_rsrc((void*)args.A2, (short)0, (int)a2_bytes, 0x00020000);
-    rb2 = __builtin_amdgcn_make_buffer_rsrc((void*)args.B2, (short)0, (int)b2_bytes, 0x00020000);
+    ra2 = rsrc(args.A2, a2_bytes);
+    rb2 = rsrc(args.B2, b2_bytes);
     sa2.prepare(args.ga, args.lda2, m0, args.M, wave, lane);
     sb2.prepare(args.gb, args.ldb2, n0, args.N, wave, lane);
   }
@@ -210,6 +181,7 @@ __global__ void __launch_bounds__(NW * 64, (LDR == 0 && NS == 2 && BM == 128 && 
   __amdgpu_buffer_rsrc_t rd = rb;
   if constexpr (LD) {
     const bf16_t* dp = args.D + (long long)lpart * LDR * args.ldd;
+    // (spelled out: through rsrc() the LDR instances schedule their prologue differently)
     rd = __builtin_amdgcn_make_buffer_rsrc((void*)dp, (short)0, (int)(((long long)(LDR - 1) * args.ldd + args.K) * 2),
                                            0x00020000);
     st.prepare(args.gb, args.ldd, 0, LDR, wave, lane);

@@ -1286,13 +1286,20 @@ def _attn_view(t: torch.Tensor, heads: int):
     return t.stride(1), t.stride(0)
 
 
-def _attn_args(q, k, v, heads, scale):
+def _attn_args(q, k, v, heads, scale, widths=None):
+    """AttnArgs of q / k / v [B, N, H*D].  widths: the head dims attn_xwide_fwd takes; None: the flash kernels' rule."""
+    _req(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention operand [B, N, H*D] bf16")
     a = _lib.AttnArgs()
     B, Nq, Cq = q.shape
     Nk = k.shape[1]
+    _req(heads >= 1 and Cq % heads == 0, "channels must split into heads")
     D = Cq // heads
+    if widths is None:
+        _req(D % 8 == 0 and D <= FLASH_MAX_D, "head dim must be a multiple of 8 and <= 160")
+    else:
+        _req(D in widths, f"attn_xwide_fwd: head dim must be one of {widths} (heads up to {FLASH_MAX_D} columns: "
+             "attn_fwd)")
     _req(k.shape[0] == B and v.shape[0] == B and v.shape[1] == Nk and k.shape[2] == Cq and v.shape[2] == Cq, "qkv")
-    _req(D % 8 == 0 and D <= FLASH_MAX_D, "head dim must be a multiple of 8 and <= 160")
     a.q, a.k, a.v = _p(q), _p(k), _p(v)
     a.ldq, a.bsq = _attn_view(q, heads)
     a.ldk, a.bsk = _attn_view(k, heads)
@@ -1413,29 +1420,16 @@ def attn_mat_fwd(q, k, v, heads, scale=None, out=None):
 def attn_xwide_fwd(q, k, v, heads, scale=None, out=None):
     """Flash attention forward for heads wider than FLASH_MAX_D (the widths in XWIDE_DIMS: the VAE's 512-wide single
     head): o = softmax(scale q k^T) v with no [Nq, Nk] buffer.  Forward only; returns o [B, Nq, H*D] bf16."""
-    _req(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention operand [B, N, H*D] bf16")
-    B, Nq, Cq = q.shape
-    Nk = k.shape[1]
-    _req(heads >= 1 and Cq % heads == 0, "channels must split into heads")
-    D = Cq // heads
-    _req(D in XWIDE_DIMS, f"attn_xwide_fwd: head dim must be one of {XWIDE_DIMS} (heads up to {FLASH_MAX_D} columns: "
-         "attn_fwd)")
-    _req(k.shape[0] == B and v.shape[0] == B and v.shape[1] == Nk and k.shape[2] == Cq and v.shape[2] == Cq, "qkv")
-    _req(Nq >= 1 and Nk >= 1 and B >= 1, "attn_xwide_fwd: empty operand")
+    a = _attn_args(q, k, v, heads, scale, widths=XWIDE_DIMS)
+    _req(a.Nq >= 1 and a.Nk >= 1 and a.B >= 1, "attn_xwide_fwd: empty operand")
     if out is None:
         out = torch.empty(q.shape, dtype=BF16, device=q.device)
     _req(out.shape == q.shape, "attn_xwide_fwd: out must have q's shape")
-    a = _lib.AttnArgs()
-    a.q, a.k, a.v, a.o = _p(q), _p(k), _p(v), _p(out)
-    a.ldq, a.bsq = _attn_view(q, heads)
-    a.ldk, a.bsk = _attn_view(k, heads)
-    a.ldv, a.bsv = _attn_view(v, heads)
+    a.o = _p(out)
     a.ldo, a.bso = _attn_view(out, heads)
     _req(_aligned(q) and _aligned(k) and _aligned(v) and _aligned(out)
          and all(s % 8 == 0 for s in (a.ldq, a.ldk, a.ldv, a.ldo, a.bsq, a.bsk, a.bsv, a.bso)),
          "attn_xwide_fwd: 16-byte aligned operands, strides in multiples of 8")
-    a.B, a.H, a.Nq, a.Nk, a.Dv = B, heads, Nq, Nk, D
-    a.scale = scale if scale is not None else D ** -0.5
     check(lib().otamd_attn_xwide_fwd(C.byref(a), stream_handle()), "otamd_attn_xwide_fwd")
     return out
 

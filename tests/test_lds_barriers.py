@@ -1,7 +1,8 @@
 """gfx950 ring kernels: no s_barrier reached with LDS reads outstanding (tools/lds_barrier_check.py) -- the barrier
 guards the slot the next LDS-DMA refills, and gfx950's s_barrier does not wait for a wave's pending ds_reads.
 attn_bwd_dq_kernel<64, 3> broke this before round 6 (a sunk MFMA took its operand wait below the barrier), which made
-dQ differ run to run.  Compiles attention.hip to device assembly (about 20 s on the CPU)."""
+dQ differ run to run.  Compiles attention.hip, attention_wide.hip and attention_vae.hip to device assembly (the
+largest in about 20 s on the CPU)."""
 import os
 import shutil
 import sys
@@ -14,12 +15,16 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") and shutil.which("hipcc") is None, reason="no hipcc")
 def test_attention_barriers_wait_for_lds_reads():
+    """each file compiled with the flags the library ships it with (build.EXTRA)"""
     import lds_barrier_check as chk
-    res = chk.scan(chk.device_asm(os.path.join(ROOT, "onetrainer_amd", "csrc", "attention.hip")))
-    names = [n for n, _, _ in res]
-    assert any("attn_bwd_dq_kernel" in n for n in names) and any("attn_fwd_kernel" in n for n in names), names
-    bad = [(n, b) for n, _, b in res if b]
-    assert not bad, bad
+    for src, kernels in (("attention.hip", ("attn_fwd_kernel", "attn_bwd_dq_kernel")),
+                         ("attention_wide.hip", ("attn_wide_fwd_kernel", "attn_wide_dq_kernel", "attn_wide_dkv_kernel")),
+                         ("attention_vae.hip", ("attn_xwide_fwd_kernel",))):
+        res = chk.scan(chk.device_asm(os.path.join(ROOT, "onetrainer_amd", "csrc", src)))
+        names = [n for n, _, _ in res]
+        assert all(any(k in n for n in names) for k in kernels), (src, names)
+        bad = [(n, b) for n, _, b in res if b]
+        assert not bad, (src, bad)
 
 
 def test_checker_flags_a_barrier_with_reads_in_flight():

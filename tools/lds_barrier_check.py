@@ -1,4 +1,4 @@
-"""Static check of gfx950 device assembly (not a test by itself; tests/test_lds_barriers.py runs it on attention.hip):
+"""Static check of gfx950 device assembly (not a test by itself; tests/test_lds_barriers.py runs it on the attention files):
 every s_barrier must be reached with no LDS access of this wave outstanding.
 
 Why: gfx950's s_barrier does not wait for a wave's outstanding ds_reads or ds_writes.  The ring kernels refill the
@@ -22,12 +22,16 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def device_asm(src: str) -> str:
+    """the device assembly of src as the library ships it: with the file's extra flags of build.py (where the
+    scheduler puts a wait relative to a barrier depends on them)"""
     if src.endswith(".s"):
         return open(src).read()
+    sys.path.insert(0, os.path.dirname(os.path.dirname(CSRC)))
+    from onetrainer_amd.build import EXTRA, hipcc
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", CSRC,
-                        "--cuda-device-only", "-S", "-o", out, src], check=True, capture_output=True)
+        subprocess.run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", CSRC, "--cuda-device-only", "-S",
+                        "-o", out, src] + EXTRA.get(os.path.basename(src), []), check=True, capture_output=True)
         return open(out).read()
 
 
