@@ -815,6 +815,26 @@ int otamd_ema_range(void* ema, const void* p, int form, long long begin, long lo
 /* replaces: nothing (the elements one sweep of the grid-stride loop of form's EMA kernel covers at the grid cap) */
 int otamd_ema_sweep_elems(int form);
 
+/* replaces: LinearFp8.forward (modules/module/quantized/LinearFp8.py:53-61) for a frozen e4m3 weight (csrc/gemm_w8.hip):
+   y[M][N] = x[M][K] dq(w8)^T (+ bias[N]) (+ residual[M][N]), dq(w8)[n][k] = bf16(bf16(w8[n][k]) * bf16(scale[n])).
+   x, y, bias, residual bf16; w8 [N][K] OCP e4m3 bytes, row stride ldw bytes; scale fp32 [N] (one entry per row, so a
+   fused q|k|v view carries each member's scalar).  K % 16 == 0, N % 8 == 0, ldx % 8 == 0, ldw % 16 == 0, ldy and
+   ldr % 4 == 0, x / w8 / y 16-byte aligned, bias / residual 8-byte aligned (OTAMD_EINVAL otherwise); x must span
+   less than 2 GiB (OTAMD_EUNSUPPORTED).  One launch, a fixed accumulation order: the same bits on every run. */
+int otamd_linear_w8(const void* x, long long ldx, const void* w8, long long ldw, const float* scale, const void* bias,
+    const void* residual, long long ldr, void* y, long long ldy, int M, int N, int K, hipStream_t s);
+/* the input gradient of the same layer: dx[M][K] = dy[M][N] dq(w8) (+ residual[M][K]); the contracts of
+   otamd_linear_w8 with dy in the place of x */
+int otamd_linear_w8_dgrad(const void* dy, long long lddy, const void* w8, long long ldw, const float* scale,
+    const void* residual, long long ldr, void* dx, long long lddx, int M, int N, int K, hipStream_t s);
+/* replaces: LinearFp8.quantize (LinearFp8.py:34-51) for w [rows][cols] contiguous (bf16, or fp32 when w_f32):
+   scale = max(max |w|, 1e-12) / 448 in fp32, w8 = e4m3 of w / scale (round to nearest even, saturating at +-448; a
+   bf16 w's quotient is rounded to bf16 first, as the reference's in-place div_ leaves it); the scalar is written to
+   scale_rows[0 .. rows).  cols % 16 == 0; w, w8 16-byte aligned; ws: 1024 floats of scratch.  Two launches (the
+   partial maxima, then the conversion); a maximum does not depend on the order, so the result is deterministic. */
+int otamd_quantize_fp8(const void* w, int w_f32, long long rows, long long cols, void* w8, float* scale_rows,
+    float* ws, hipStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -312,6 +312,10 @@ SIGNATURES: dict[str, list] = {
     "otamd_cfg_ddim_step": [VP, VP, VP, VP, I, LL, F, F, I, VP, VP, I, I, I, VP, LL, VP],
     "otamd_cfg_ddim_step_ws_bytes": [I, LL],
     "otamd_nhwc_to_rgb8": [VP, I, LL, VP, VP],
+    # gemm_w8.hip
+    "otamd_linear_w8": [VP, LL, VP, LL, VP, VP, VP, LL, VP, LL, I, I, I, VP],
+    "otamd_linear_w8_dgrad": [VP, LL, VP, LL, VP, VP, LL, VP, LL, I, I, I, VP],
+    "otamd_quantize_fp8": [VP, I, LL, LL, VP, VP, VP, VP],
 }
 
 _lib = None

@@ -690,6 +690,81 @@ def linear_dgrad(dy: torch.Tensor, w: torch.Tensor, out=None, residual=None, acc
     return out
 
 
+# ---- frozen e4m3 weights (weight_dtype FLOAT_8, csrc/gemm_w8.hip) ----------------------------------------------
+def quantize_fp8(w: torch.Tensor, out=None, scale_rows=None):
+    """LinearFp8.quantize on the device: w [N, K] bf16 / fp32 -> (w8 uint8 [N, K] of e4m3 bytes, scale fp32 [N]) with
+    scale = max(|w|.max(), 1e-12) / 448 in every row's entry.  out / scale_rows: the caller's slices of a weight
+    buffer and of a row-scale vector (a member of a fused q|k|v view writes its own rows)."""
+    _req(w.is_cuda and w.dtype in (BF16, F32) and w.dim() == 2 and w.is_contiguous(), "quantize_fp8: [N,K] bf16/f32")
+    N, K = w.shape
+    _req(N >= 1 and K >= 16 and K % 16 == 0, "quantize_fp8: K must be a multiple of 16")
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    if scale_rows is None:
+        scale_rows = torch.empty(N, dtype=F32, device=w.device)
+    _req(out.dtype == torch.uint8 and out.shape == (N, K) and out.is_contiguous(), "quantize_fp8 out: uint8 [N,K]")
+    _req(scale_rows.dtype == F32 and scale_rows.shape == (N,) and scale_rows.is_contiguous(), "scale rows: f32 [N]")
+    _req(_aligned(w) and _aligned(out), "16-byte aligned operands required")
+    _req(out.device == w.device and scale_rows.device == w.device, "quantize_fp8: every operand on w's device")
+    ws = workspace(4096, w.device)
+    check(lib().otamd_quantize_fp8(_p(w), int(w.dtype == F32), N, K, _p(out), _p(scale_rows), _p(ws),
+                                   stream_handle()), "otamd_quantize_fp8")
+    return out, scale_rows
+
+
+def _w8_operands(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, kc: int, what: str, *others):
+    _req(a.is_cuda and a.dtype == BF16 and a.dim() == 2 and a.shape[1] == kc, f"{what}: bf16 cuda [M,{kc}] input")
+    _req(w8.dtype == torch.uint8 and w8.dim() == 2 and w8.stride(1) == 1, f"{what}: uint8 (e4m3) [N,K] weight")
+    N, K = w8.shape
+    _req(K % 16 == 0 and N % 8 == 0, f"{what}: K must be a multiple of 16 and N of 8")
+    _req(w8.stride(0) % 16 == 0, f"{what}: weight row stride must be a multiple of 16 bytes")
+    _req(scale.dtype == F32 and scale.shape == (N,) and scale.is_contiguous(), f"{what}: f32 [N] row scales")
+    _req(_aligned(a) and _aligned(w8), "16-byte aligned operands required")
+    _req(((a.shape[0] - 1) * _ld_rows(a) + kc) * 2 < 2 ** 31, f"{what}: input larger than 2 GiB")
+    _req(all(t is None or t.device == a.device for t in (w8, scale) + tuple(others)),
+         f"{what}: every operand on the input's device")
+
+
+def _w8_out(out, residual, M, NO, device):
+    out = _out(out, M, NO, BF16, device)
+    _req(out.dtype == BF16 and _aligned(out), "out: bf16, 16-byte aligned")
+    ldr = 0
+    if residual is not None:
+        _req(residual.dtype == BF16 and residual.shape == (M, NO) and residual.stride(1) == 1 and
+             residual.data_ptr() % 8 == 0 and (M == 1 or residual.stride(0) % 4 == 0), "residual: bf16 [M,N]")
+        ldr = residual.stride(0) if M > 1 else NO
+    return out, ldr
+
+
+def linear_w8(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, bias=None, residual=None,
+              out=None) -> torch.Tensor:
+    """y[M,N] = x[M,K] @ dq(w8)^T (+bias[N]) (+residual), dq(w8)[n,k] = bf16(bf16(w8[n,k]) * bf16(scale[n])): the
+    forward of a frozen LinearFp8 (w8: e4m3 bytes as uint8 [N,K], scale: f32 [N])."""
+    N, K = w8.shape if w8.dim() == 2 else (0, 0)
+    _w8_operands(x, w8, scale, K, "linear_w8", bias, residual, out)
+    M = x.shape[0]
+    if bias is not None:
+        _req(bias.dtype == BF16 and bias.numel() == N and bias.is_contiguous() and bias.data_ptr() % 8 == 0,
+             "bias: bf16 [N]")
+    out, ldr = _w8_out(out, residual, M, N, x.device)
+    check(lib().otamd_linear_w8(_p(x), _ld_rows(x), _p(w8), w8.stride(0) if N > 1 else K, _p(scale), _p(bias),
+                                _p(residual), ldr, _p(out), out.stride(0) if M > 1 else N, M, N, K,
+                                stream_handle()), "otamd_linear_w8")
+    return out
+
+
+def linear_w8_dgrad(dy: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, residual=None, out=None) -> torch.Tensor:
+    """dx[M,K] = dy[M,N] @ dq(w8) (+residual[M,K]): the input gradient of linear_w8 (no weight gradient exists)."""
+    N, K = w8.shape if w8.dim() == 2 else (0, 0)
+    _w8_operands(dy, w8, scale, N, "linear_w8_dgrad", residual, out)
+    M = dy.shape[0]
+    out, ldr = _w8_out(out, residual, M, K, dy.device)
+    check(lib().otamd_linear_w8_dgrad(_p(dy), _ld_rows(dy), _p(w8), w8.stride(0) if N > 1 else K, _p(scale),
+                                      _p(residual), ldr, _p(out), out.stride(0) if M > 1 else K, M, N, K,
+                                      stream_handle()), "otamd_linear_w8_dgrad")
+    return out
+
+
 def _bias_grad(a: GemmArgs, bias_grad, bias_acc: bool, n: int):
     """fuse the bias gradient sum_t dy[t, :] into a weight-gradient GEMM (GemmArgs.colsum)."""
     if bias_grad is not None:

@@ -27,7 +27,7 @@ from .. import kernels as K
 from . import functional as Fn
 from . import streams as S
 from . import flux_ops as O
-from .param_store import FlatParamStore
+from .param_store import FlatParamStore, fp8_eligible
 
 BF16 = torch.bfloat16
 
@@ -155,14 +155,19 @@ def rope_tables(L: int, h: int, w: int, cfg: FluxConfig):
 
 class FluxTransformer2DModel:
     def __init__(self, cfg: FluxConfig, device, dtype=BF16, seed: int | None = 0, group: str = "transformer",
-                 trainable: bool = True, master: bool = False):
+                 trainable: bool = True, master: bool = False, fp8: bool = False):
+        """fp8: the frozen network's Linear weights as e4m3 (weight_dtype FLOAT_8); norms and biases keep bf16"""
         if cfg.attention_head_dim != 128 or sum(cfg.axes_dims_rope) != 128:
             raise NotImplementedError("the q/k norm + RoPE kernel is built for 128-wide heads")
         self.cfg = cfg
         self.device = torch.device(device)
         self.specs = flux_specs(cfg)
         self.store = FlatParamStore([(n, sh, group) for n, sh, _, _ in self.specs], dtype, self.device,
-                                    trainable=trainable, master=master)
+                                    trainable=trainable, master=master,
+                                    fp8=[n for n, sh, k, _ in self.specs if fp8 and k == "linear" and fp8_eligible(sh)])
+        # Linear weights of an fp8 network whose shape the e4m3 GEMMs do not take: kept bf16, recorded by create_model
+        self.fp8_kept_bf16 = [n for n, sh, k, _ in self.specs if fp8 and k == "linear" and len(sh) == 2
+                              and not fp8_eligible(sh)]
         self.config = {"guidance_embeds": cfg.guidance_embeds}
         self.lora = None
         self._refs: dict = {}
@@ -209,7 +214,10 @@ class FluxTransformer2DModel:
             for name, shape, *_ in self.specs:
                 if tuple(sd[name].shape) != tuple(shape):
                     raise ValueError(f"{name}: shape {tuple(sd[name].shape)} != {shape}")
-                self.store.write(name, sd[name].to(self.device, torch.float32))
+                # an fp8 weight is quantised from the checkpoint's own dtype, as LinearFp8.quantize does (a bf16
+                # weight's quotient is rounded to bf16 first); everything else goes through fp32
+                keep = name in self.store.fp8_rows and sd[name].dtype == BF16
+                self.store.write(name, sd[name].to(self.device, BF16 if keep else torch.float32))
 
     def R(self, names, shape=None) -> Fn.PRef:
         key = (tuple(names) if isinstance(names, (list, tuple)) else names, shape)

@@ -16,6 +16,7 @@ import torch
 from .. import kernels as K
 from . import streams as S
 from .functional import _trainable_params
+from .param_store import W8Ref
 
 
 class ModState:
@@ -60,10 +61,17 @@ class RowsLinearFn(torch.autograd.Function):
                 drop = site.drop()
                 if drop is not None:   # LoRA dropout: each segment's t has its own row index starting at 0
                     drop.dropout(t, site)
-                K.linear(xs, wref.w, bias=bref.w if bref is not None else None, lora=(t, site.up2), out=y[r0:r1])
+                if isinstance(wref.w, W8Ref):   # fp8 base: the up projection enters through the residual input
+                    K.linear_w8(xs, wref.w.w8, wref.w.scale, bias=bref.w if bref is not None else None,
+                                residual=K.linear(t, site.up2), out=y[r0:r1])
+                else:
+                    K.linear(xs, wref.w, bias=bref.w if bref is not None else None, lora=(t, site.up2), out=y[r0:r1])
                 ts.append(t)
             else:
-                K.linear(xs, wref.w, bias=bref.w if bref is not None else None, out=y[r0:r1])
+                if isinstance(wref.w, W8Ref):
+                    K.linear_w8(xs, wref.w.w8, wref.w.scale, bias=bref.w if bref is not None else None, out=y[r0:r1])
+                else:
+                    K.linear(xs, wref.w, bias=bref.w if bref is not None else None, out=y[r0:r1])
                 ts.append(None)
         ctx.save_for_backward(x)
         ctx.segs, ctx.ts = segs, ts
@@ -97,7 +105,10 @@ class RowsLinearFn(torch.autograd.Function):
                     elif btr:
                         K.colsum(dys, out=bref.g.view(1, -1), accumulate=bref.acc())
             if dx is not None:
-                if site is not None:
+                if isinstance(wref.w, W8Ref):   # fp8 base: u A enters through the residual input
+                    K.linear_w8_dgrad(dys, wref.w.w8, wref.w.scale, out=dx[r0:r1],
+                                      residual=K.linear_dgrad(u, site.down) if site is not None else None)
+                elif site is not None:
                     K.linear_dgrad(dys, wref.w, lora=(u, site.down), out=dx[r0:r1])
                 else:
                     K.linear_dgrad(dys, wref.w, out=dx[r0:r1])

@@ -16,6 +16,7 @@ import torch
 
 from .. import kernels as K
 from . import streams as S
+from .param_store import W8Ref
 
 
 class PRef:
@@ -164,6 +165,9 @@ _WONLY_SIDE = os.environ.get("OTAMD_WGRAD_ONLY_SIDE", "1") != "0"
 
 
 def linear(x, wref, bref=None, residual=None, lora=None):
+    w8 = getattr(wref, "_w", None)
+    if isinstance(w8, W8Ref):   # a frozen e4m3 weight of an fp8 store (weight_dtype FLOAT_8)
+        return linear_w8(x, w8, bref, residual, lora)
     if lora is not None:
         return LoraLinearFn.apply(x, wref, bref, residual, lora, *lora.params, *_trainable_params(wref, bref))
     return LinearFn.apply(x, wref, bref, residual, *_params(wref, bref))
@@ -258,6 +262,85 @@ class LoraLinearFn(torch.autograd.Function):
             bref.done()
         dres = dy if ctx.has_res else None
         return (dx, None, None, dres, None) + (None,) * (len(ctx.needs_input_grad) - 5)
+
+
+def _bias_w(bref):
+    if bref is not None and bref.trainable:
+        raise ValueError("a frozen fp8 Linear has a frozen bias")
+    return bref.w if bref is not None else None
+
+
+def _dy_rows(dy):
+    dy2 = _rows(dy)
+    return dy2.contiguous() if dy2.stride(1) != 1 or dy2.stride(0) % 8 or dy2.data_ptr() % 16 else dy2
+
+
+class LinearW8Fn(torch.autograd.Function):
+    """y = x dq(W8)^T (+b) (+residual) for a frozen e4m3 weight (kernels.linear_w8); backward: dx = dy dq(W8)
+    (kernels.linear_w8_dgrad).  No weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, wref, bref, residual):
+        x2 = _rows(x)
+        y = K.linear_w8(x2, wref.w8, wref.scale, bias=_bias_w(bref),
+                        residual=_rows(residual) if residual is not None else None)
+        ctx.wref, ctx.has_res, ctx.xshape = wref, residual is not None, x.shape
+        return y.view(*x.shape[:-1], wref.w8.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        wref = ctx.wref
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.linear_w8_dgrad(_dy_rows(dy), wref.w8, wref.scale).view(ctx.xshape)
+        return dx, None, None, dy if ctx.has_res else None
+
+
+class LoraLinearW8Fn(torch.autograd.Function):
+    """LoraLinearFn over a frozen e4m3 base: the two-launch LoRA form around the fp8 base GEMM.  Forward: t = x A^T
+    (bf16 GEMM, masked in place under LoRA dropout), r = t (sB)^T (+residual), y = x dq(W8)^T (+b) + r with r as the
+    base GEMM's residual input.  Backward: u = dy (sB) and the adapter weight gradients as in LoraLinearFn;
+    dx = dy dq(W8) + u A with u A as the input-gradient GEMM's residual input."""
+
+    @staticmethod
+    def forward(ctx, x, wref, bref, residual, site, *params):
+        x2 = _rows(x)
+        t = K.linear(x2, site.down)
+        drop = site.drop()
+        if drop is not None:
+            drop.dropout(t, site)
+        r = K.linear(t, site.up2, residual=_rows(residual) if residual is not None else None)
+        y = K.linear_w8(x2, wref.w8, wref.scale, bias=_bias_w(bref), residual=r)
+        ctx.save_for_backward(x2, t)
+        ctx.wref, ctx.site, ctx.has_res, ctx.xshape = wref, site, residual is not None, x.shape
+        return y.view(*x.shape[:-1], wref.w8.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, t = ctx.saved_tensors
+        wref, site = ctx.wref, ctx.site
+        dy2 = _dy_rows(dy)
+        u = K.linear_dgrad(dy2, site.up2)
+        drop = site.drop()
+        if drop is not None:   # the forward's mask, drawn again: before both readers of u
+            drop.dropout(u, site)
+        with S.wgrad_region((dy2, x2, t, u)):
+            acc, r = site.acc(), site.rank
+            K.linear_wgrad(u, x2, out=site.g_down, accumulate=acc)
+            for p, (g, (n0, n1)) in enumerate(zip(site.g_up, site.ranges)):
+                K.linear_wgrad(dy2[:, n0:n1], t[:, p * r:(p + 1) * r], out=g, accumulate=acc, alpha=site.scale)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.linear_w8_dgrad(dy2, wref.w8, wref.scale, residual=K.linear_dgrad(u, site.down)).view(ctx.xshape)
+        site.done()
+        return (dx, None, None, dy if ctx.has_res else None, None) + (None,) * (len(ctx.needs_input_grad) - 5)
+
+
+def linear_w8(x, wref: W8Ref, bref=None, residual=None, lora=None):
+    """a frozen fp8 Linear (W8Ref), optionally under a plain-LoRA site"""
+    if lora is not None:
+        return LoraLinearW8Fn.apply(x, wref, bref, residual, lora, *lora.params)
+    return LinearW8Fn.apply(x, wref, bref, residual)
 
 
 class ConvFn(torch.autograd.Function):

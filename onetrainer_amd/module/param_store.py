@@ -17,6 +17,43 @@ from dataclasses import dataclass
 import torch
 
 
+class W8Ref:
+    """A frozen e4m3 Linear weight (weight_dtype FLOAT_8, LinearFp8.py): `w8` uint8 [N, K] of e4m3 bytes and `scale`
+    fp32 [N], one entry per row, so the weights one GEMM consumes together (to_q|to_k|to_v) are one W8Ref whose rows
+    carry their member's scalar.  Never trainable: there is no weight gradient."""
+    __slots__ = ("w8", "scale")
+
+    def __init__(self, w8: torch.Tensor, scale: torch.Tensor):
+        self.w8, self.scale = w8, scale
+
+    @property
+    def shape(self):
+        return self.w8.shape
+
+    @classmethod
+    def quantize(cls, members) -> "W8Ref":
+        """members: the bf16 / fp32 [n_i, K] weights of one (fused) GEMM, quantised on the device one by one
+        (kernels.quantize_fp8: each with its own per-tensor scale) into one buffer"""
+        from .. import kernels as K
+        rows, k = sum(m.shape[0] for m in members), members[0].shape[1]
+        w8 = torch.empty((rows, k), dtype=torch.uint8, device=members[0].device)
+        scale = torch.empty(rows, dtype=torch.float32, device=members[0].device)
+        r0 = 0
+        for m in members:
+            K.quantize_fp8(m.contiguous(), out=w8[r0:r0 + m.shape[0]], scale_rows=scale[r0:r0 + m.shape[0]])
+            r0 += m.shape[0]
+        return cls(w8, scale)
+
+    def dequantized(self) -> torch.Tensor:
+        """the bf16 weight the kernels multiply by: weight.to(bf16).mul_(scale) of LinearFp8.forward"""
+        return self.w8.view(torch.float8_e4m3fn).to(torch.bfloat16) * self.scale.to(torch.bfloat16)[:, None]
+
+
+def fp8_eligible(shape) -> bool:
+    """a Linear weight [N, K] the e4m3 GEMMs take (csrc/gemm_w8.hip): K in 16-groups, N in 8-groups"""
+    return len(shape) == 2 and shape[1] % 16 == 0 and shape[0] % 8 == 0
+
+
 @dataclass
 class Slot:
     name: str
@@ -27,7 +64,7 @@ class Slot:
 
 
 class FlatParamStore:
-    def __init__(self, specs, dtype, device, align_bytes=16, trainable=True, master=False):
+    def __init__(self, specs, dtype, device, align_bytes=16, trainable=True, master=False, fp8=()):
         """specs: iterable of (name, shape, group) in layout order.  trainable=False: a frozen base
         (LoRA training, unet.requires_grad_(False) in StableDiffusionXLLoRASetup.py:78-86): no grad
         buffer, parameters do not require grad, backward kernels skip its weight gradients.
@@ -40,17 +77,30 @@ class FlatParamStore:
         self.dtype, self.device = dtype, device
         self.slots: dict[str, Slot] = {}
         self.order: list[str] = []
-        off = 0
+        self.fp8_rows: dict[str, int] = {}   # fp8 weight -> its first row in scale_rows
+        fp8 = set(fp8)
+        if fp8 and trainable:
+            raise ValueError("fp8 weights belong to a frozen store")
+        off = off8 = rows8 = 0
         for name, shape, group in specs:
             n = 1
             for s in shape:
                 n *= int(s)
-            off = (off + al - 1) // al * al
-            self.slots[name] = Slot(name, tuple(int(s) for s in shape), off, n, group)
+            if name in fp8:   # n is a multiple of 16 bytes (fp8_eligible): adjacent weights stay adjacent
+                if not fp8_eligible(shape):
+                    raise ValueError(f"{name} {tuple(shape)}: not a Linear weight the e4m3 GEMMs take")
+                self.slots[name] = Slot(name, tuple(int(s) for s in shape), off8, n, group)
+                self.fp8_rows[name] = rows8
+                off8, rows8 = off8 + n, rows8 + int(shape[0])
+            else:
+                off = (off + al - 1) // al * al
+                self.slots[name] = Slot(name, tuple(int(s) for s in shape), off, n, group)
+                off += n
             self.order.append(name)
-            off += n
         self.numel = (off + al - 1) // al * al
         self.trainable = trainable
+        self.data8 = torch.zeros(off8, dtype=torch.uint8, device=device) if fp8 else None
+        self.scale_rows = torch.zeros(rows8, dtype=torch.float32, device=device) if fp8 else None
         self.data = torch.zeros(self.numel, dtype=dtype, device=device)
         if master and (not trainable or dtype != torch.bfloat16):
             raise ValueError("fp32 master weights back a trainable bf16 store")
@@ -59,7 +109,8 @@ class FlatParamStore:
         self._params: dict[str, torch.nn.Parameter] = {}
         for name in self.order:
             s = self.slots[name]
-            p = torch.nn.Parameter(self.data[s.offset:s.offset + s.numel].view(s.shape), requires_grad=trainable)
+            buf = self.data8 if name in self.fp8_rows else self.data
+            p = torch.nn.Parameter(buf[s.offset:s.offset + s.numel].view(s.shape), requires_grad=trainable)
             if trainable:
                 p.grad = self.grad[s.offset:s.offset + s.numel].view(s.shape)
             self._params[name] = p
@@ -93,9 +144,16 @@ class FlatParamStore:
             if s.offset != end:
                 raise ValueError(f"parameters {names} are not adjacent in the flat store")
             end += s.numel
+        n8 = sum(n in self.fp8_rows for n in names)
+        if n8 and n8 != len(names):
+            raise ValueError(f"parameters {names} mix fp8 and bf16 weights")
         buf = self.grad if grad else self.data
         if buf is None:
             return None
+        if n8:
+            w8 = self.data8[first.offset:end].view(shape if shape is not None else first.shape)
+            r0 = self.fp8_rows[names[0]]
+            return W8Ref(w8, self.scale_rows[r0:r0 + w8.shape[0]])
         if not grad and self.update_events is not None:
             self.wait_params(end)
         v = buf[first.offset:end]
@@ -108,6 +166,8 @@ class FlatParamStore:
     def value(self, name):
         """the trained value of one tensor (store layout): the fp32 master view, else the parameter view."""
         s = self.slots[name]
+        if name in self.fp8_rows:   # what the kernels multiply by (bf16)
+            return self.view(name).dequantized()
         if self.master is not None:
             return self.master[s.offset:s.offset + s.numel].view(s.shape)
         return self.params[name].detach()
@@ -117,6 +177,13 @@ class FlatParamStore:
         """set one tensor (store layout); with master weights the fp32 value goes to the master and the working
         copy takes its bf16 cast."""
         s = self.slots[name]
+        if name in self.fp8_rows:   # LinearFp8.quantize, on the device, as the weight is loaded
+            from .. import kernels as K
+            v = value.to(self.device)
+            v = v if v.dtype in (torch.bfloat16, torch.float32) else v.float()
+            ref = self.view(name)
+            K.quantize_fp8(v.reshape(s.shape).contiguous(), out=ref.w8, scale_rows=ref.scale)
+            return
         if self.master is not None:
             self.wait_params()
             mv = self.master[s.offset:s.offset + s.numel].view(s.shape)

@@ -25,7 +25,7 @@ import torch
 
 from .. import kernels as K
 from . import functional as Fn
-from .param_store import FlatParamStore
+from .param_store import FlatParamStore, fp8_eligible
 
 BF16 = torch.bfloat16
 
@@ -233,13 +233,19 @@ class UNet2DConditionModel:
     """HIP UNet; parameters live in `self.store` (FlatParamStore)."""
 
     def __init__(self, cfg: UNetConfig, device, dtype=BF16, seed: int | None = 0, group: str = "unet",
-                 trainable: bool = True, master: bool = False):
+                 trainable: bool = True, master: bool = False, fp8: bool = False):
+        """fp8: the frozen network's nn.Linear weights as e4m3 (weight_dtype FLOAT_8); convolutions (1x1 ones held
+        as linears included), norms and biases keep bf16"""
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
         self.specs = unet_specs(cfg)
         self.store = FlatParamStore([(n, _store_shape(n, sh, k, cfg), group) for n, sh, k, _ in self.specs],
-                                    dtype, self.device, trainable=trainable, master=master)
+                                    dtype, self.device, trainable=trainable, master=master,
+                                    fp8=[n for n, sh, k, _ in self.specs if fp8 and k == "linear" and fp8_eligible(sh)])
+        # Linear weights of an fp8 network whose shape the e4m3 GEMMs do not take: kept bf16, recorded by create_model
+        self.fp8_kept_bf16 = [n for n, sh, k, _ in self.specs if fp8 and k == "linear" and len(sh) == 2
+                              and not fp8_eligible(sh)]
         self._refs: dict = {}
         self.lora = None      # module/lora.py LoRAUNetWrapper when training adapters on a frozen base
         self.dora = None      # module/dora.py DoRAWrapper instead, with lora_decompose: adapted GEMMs read merged weights
@@ -307,7 +313,10 @@ class UNet2DConditionModel:
             for name, shape, kind, _ in self.specs:
                 if tuple(sd[name].shape) != tuple(shape):
                     raise ValueError(f"{name}: shape {tuple(sd[name].shape)} != {shape}")
-                self._assign(name, sd[name].to(self.device, torch.float32), kinds[name])
+                # an fp8 weight is quantised from the checkpoint's own dtype, as LinearFp8.quantize does (a bf16
+                # weight's quotient is rounded to bf16 first); everything else goes through fp32
+                keep = name in self.store.fp8_rows and sd[name].dtype == BF16
+                self._assign(name, sd[name].to(self.device, BF16 if keep else torch.float32), kinds[name])
 
     def R(self, names, shape=None) -> Fn.PRef:
         if self.dora is not None:   # an adapted base GEMM runs on its merged weight W' (module/dora.py DoraRef)
@@ -365,7 +374,7 @@ class UNet2DConditionModel:
         The reference runs one [B*77, 2C] GEMM per block (70 per SDXL forward, ~25 us each at M = 308);
         this is 11 launches.  Backward stays per block (PrecomputedLinearFn).  None when not applicable
         (LoRA / DoRA on the projection, a single block, irregular layout)."""
-        if depth < 2 or self.lora is not None or self.dora is not None:
+        if depth < 2 or self.lora is not None or self.dora is not None or self.store.fp8_rows:
             return None
         names = [(f"{p}.transformer_blocks.{k}.attn2.to_k.weight", f"{p}.transformer_blocks.{k}.attn2.to_v.weight")
                  for k in range(depth)]

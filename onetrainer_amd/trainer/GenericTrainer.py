@@ -88,7 +88,8 @@ class GenericTrainer(TimedActionMixin):
         self.model_setup.setup_model(self.model, cfg)
         self.model_setup.setup_train_device(self.model, cfg)
         plan = getattr(self.model, "dtype_plan", None)
-        if plan is not None and plan.overrides and self.rank == 0:   # util/dtype_util.py: recorded, not silent
+        if plan is not None and (plan.overrides or plan.network == "FLOAT_8") and self.rank == 0:
+            # util/dtype_util.py: deviations recorded, not silent; an fp8 frozen base is named
             print(f"dtype policy: {plan.summary()}", flush=True)
         self.parameters = self.model.parameters.parameters()
         import os

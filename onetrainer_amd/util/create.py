@@ -39,9 +39,10 @@ def create_model(config, device, seed=0, unet_config=None, prediction_type="epsi
         from ..model.FluxModel import FluxModel
         from ..module import flux as FX
         tr = FX.FluxTransformer2DModel(flux_config or FX.flux_dev_config(), device, seed=seed,
-                                       trainable=config.training_method != "LORA", master=plan.master)
+                                       trainable=config.training_method != "LORA", master=plan.master,
+                                       fp8=plan.network == "FLOAT_8")
         m = FluxModel(tr, model_type=mt)
-        m.dtype_plan = plan
+        m.dtype_plan = _record_kept_bf16(plan, tr)
         return m
     if unet_config is None:
         unet_config = _unet_config_on_disk(config)
@@ -55,11 +56,21 @@ def create_model(config, device, seed=0, unet_config=None, prediction_type="epsi
         unet_config.in_channels = unet_in_channels(mt)
     check_in_channels(mt, unet_config.in_channels, unet_config.block_out_channels[0])
     unet = U.UNet2DConditionModel(unet_config, device, seed=seed, trainable=config.training_method != "LORA",
-                                  master=plan.master)
+                                  master=plan.master, fp8=plan.network == "FLOAT_8")
     ns = NoiseScheduler(device, prediction_type=prediction_type)
     m = StableDiffusionXLModel(unet, ns, SCALING.get(mt, 0.13025), model_type=mt)
-    m.dtype_plan = plan
+    m.dtype_plan = _record_kept_bf16(plan, unet)
     return m
+
+
+def _record_kept_bf16(plan, net):
+    """an fp8 network's Linear weights that stay bf16 (K % 16 or N % 8: csrc/gemm_w8.hip takes neither) become an
+    override record of the plan: recorded, not silent"""
+    kept = getattr(net, "fp8_kept_bf16", [])
+    if kept:
+        plan.overrides.append({"field": f"{len(kept)} Linear weights ({kept[0]}, ...)", "reference": "FLOAT_8",
+                               "build": "BFLOAT_16", "reason": "K % 16 != 0 or N % 8 != 0: outside the e4m3 GEMMs"})
+    return plan
 
 
 def _unet_config_on_disk(config):

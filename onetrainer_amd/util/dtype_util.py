@@ -16,12 +16,14 @@ fp32) and store the trained network in bf16 (full fine-tune, bf16 weights), in f
 working copy (full fine-tune, FLOAT_32 weights: module/param_store.py `master`, csrc/adamw.hip
 adamw_master_kernel), or keep a frozen bf16 base plus fp32 adapters (LoRA).  `dtype_plan(cfg)` maps a config
 onto that:
-  * the same decision as the reference -> taken;
+  * the same decision as the reference -> taken; that includes a frozen LoRA base in FLOAT_8: the network's Linear
+    weights are held as e4m3 with per-tensor scales and multiplied by csrc/gemm_w8.hip (LinearFp8.py);
   * a decision that only changes precision in a direction the build supports -> taken with an OVERRIDE
     record (field, reference value, build value, reason), logged once by the trainer and kept on the model
     (`model.dtype_plan`): FLOAT_16 compute -> BFLOAT_16 (SURVEY.md §8(d) C3 prescribes exactly this); a frozen
     base in FLOAT_16 / FLOAT_32 / a quantized format -> stored BFLOAT_16 (autocast casts frozen weights to the
-    compute dtype anyway; NF4 / int8 need bitsandbytes, CUDA-only); bf16 / fp16 adapters -> kept fp32; the
+    compute dtype anyway; NF4 / int8 need bitsandbytes, CUDA-only; FLOAT_8 with DoRA, which merges weights every
+    step); bf16 / fp16 adapters -> kept fp32; the
     reference's GradScaler -> not needed with bf16 compute;
   * a decision the build cannot honour -> ValueError before any weight is allocated: fp32 / tf32 compute, a
     trained network in a quantized format.
@@ -91,9 +93,10 @@ class DtypePlan:
     overrides: list = field(default_factory=list)   # [{field, reference, build, reason}]
 
     def summary(self) -> str:
+        head = f"network {self.network}: " if self.network == "FLOAT_8" else ""
         if not self.overrides:
-            return "dtypes as configured (bf16 compute)"
-        return "; ".join(f"{o['field']} {o['reference']} -> {o['build']} ({o['reason']})" for o in self.overrides)
+            return head + "dtypes as configured (bf16 compute)"
+        return head + "; ".join(f"{o['field']} {o['reference']} -> {o['build']} ({o['reason']})" for o in self.overrides)
 
 
 def dtype_plan(cfg) -> DtypePlan:
@@ -129,8 +132,11 @@ def dtype_plan(cfg) -> DtypePlan:
                                    "reason": "bf16 storage of the trained network (no fp16 kernels)"})
         elif n != BF16:
             raise ValueError(f"{net_field} {n} is not supported")
+    elif n == "FLOAT_8" and not getattr(cfg, "lora_decompose", False):
+        plan.network = "FLOAT_8"   # frozen Linear weights as e4m3 with per-tensor scales (LinearFp8.py; csrc/gemm_w8.hip)
     elif n != BF16:
-        why = ("quantized base formats need bitsandbytes (CUDA-only, out of scope)" if n in QUANTIZED else
+        why = ("DoRA merges the adapted weights every step and stays on a bf16 base" if n == "FLOAT_8" else
+               "NF4 / int8 base formats need bitsandbytes (CUDA-only, out of scope)" if n in QUANTIZED else
                "frozen base stored in the bf16 compute dtype (autocast casts it to the compute dtype anyway)")
         plan.overrides.append({"field": net_field, "reference": n, "build": BF16, "reason": why})
 
