@@ -28,7 +28,11 @@ enum { OTAMD_OK = 0, OTAMD_EINVAL = 1, OTAMD_ELAUNCH = 2, OTAMD_EUNSUPPORTED = 3
 enum { OPM_K = 0, OPM_MN = 1, OPM_CONV_FWD = 2, OPM_CONV_DGRAD = 3, OPM_CONV_WGRAD = 4 };
 
 typedef struct ConvGeom {
-  int N, SH, SW, SC, RH, RW, KH, KW, stride, pad, upsample, pad_;
+  int N, SH, SW, SC, RH, RW, KH, KW, stride, pad, upsample;
+  /* circular padding (padding_mode 'circular'): non-zero makes a tap inside the padding margin read the pixel on the
+     opposite edge of the same image instead of zero; needs pad <= H, W and 2 pad <= K - 1.  0: zero padding.
+     pad_ is the field's earlier, reserved name. */
+  union { int circular; int pad_; };
   long long ld;
 } ConvGeom;
 

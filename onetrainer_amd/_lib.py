@@ -19,7 +19,7 @@ _ERR = {1: "invalid arguments (shape/alignment contract)", 2: "kernel launch fai
 class ConvGeom(C.Structure):
     _fields_ = [("N", C.c_int), ("SH", C.c_int), ("SW", C.c_int), ("SC", C.c_int), ("RH", C.c_int),
                 ("RW", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
-                ("upsample", C.c_int), ("pad_", C.c_int), ("ld", C.c_longlong)]
+                ("upsample", C.c_int), ("circular", C.c_int), ("ld", C.c_longlong)]   # circular: otamd.h's pad_
 
 
 class GemmArgs(C.Structure):

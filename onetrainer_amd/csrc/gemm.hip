@@ -68,9 +68,9 @@ __device__ __forceinline__ void kmode_prepare(const ConvGeom& g, int mn0, int MN
 }
 
 // load this thread's 4 chunks of a K-mode tile (rows mn0.., k chunk k0 + 8*(tid&7))
-template <int MODE>
-__device__ __forceinline__ void kmode_load(const bf16_t* __restrict__ X, long long ld, const ConvGeom& g, int mn0,
-                                           int k0, int K, const RowCtx& rc, bf8 (&st)[4]) {
+template <int MODE, bool WRAP>
+__device__ __forceinline__ void kmode_load_form(const bf16_t* __restrict__ X, long long ld, const ConvGeom& g, int mn0,
+                                                int k0, int K, const RowCtx& rc, bf8 (&st)[4]) {
   const int tid = threadIdx.x;
   const int k = k0 + 8 * (tid & 7);
   const bool kok = k < K;
@@ -89,7 +89,8 @@ __device__ __forceinline__ void kmode_load(const bf16_t* __restrict__ X, long lo
       bool ok = kok && rc.ok[i];
       int sy, sx;
       if (MODE == OPM_CONV_FWD) {
-        const int y = rc.y0[i] + r, x = rc.x0[i] + s;
+        int y = rc.y0[i] + r, x = rc.x0[i] + s;
+        if (WRAP) { const int u = g.upsample ? 2 : 1; y = wrap_tap(y, u * g.SH, g.pad); x = wrap_tap(x, u * g.SW, g.pad); }
         if (g.upsample) {
           ok = ok && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW;
           sy = y >> 1; sx = x >> 1;
@@ -98,7 +99,8 @@ __device__ __forceinline__ void kmode_load(const bf16_t* __restrict__ X, long lo
           sy = y; sx = x;
         }
       } else {  // dgrad: source pixel ((h+pad-r)/st, (w+pad-s)/st) when divisible
-        const int ty = rc.y0[i] - r, tx = rc.x0[i] - s;
+        int ty = rc.y0[i] - r, tx = rc.x0[i] - s;
+        if (WRAP && g.pad > 0) { ty = wrap_grad(ty, g.RH); tx = wrap_grad(tx, g.RW); }
         if (g.stride == 1) { sy = ty; sx = tx; }
         else {
           ok = ok && ty >= 0 && tx >= 0 && (ty % g.stride) == 0 && (tx % g.stride) == 0;
@@ -109,6 +111,14 @@ __device__ __forceinline__ void kmode_load(const bf16_t* __restrict__ X, long lo
       st[i] = ok ? ld8(X + ((long long)(rc.n[i] * g.SH + sy) * g.SW + sx) * g.ld + ch) : zero8();
     }
   }
+}
+
+// circular padding (ConvGeom.circular): one launch-uniform branch per tile; the other form is the code without it
+template <int MODE>
+__device__ __forceinline__ void kmode_load(const bf16_t* __restrict__ X, long long ld, const ConvGeom& g, int mn0,
+                                           int k0, int K, const RowCtx& rc, bf8 (&st)[4]) {
+  if (MODE != OPM_K && g.circular) kmode_load_form<MODE, true>(X, ld, g, mn0, k0, K, rc, st);
+  else kmode_load_form<MODE, false>(X, ld, g, mn0, k0, K, rc, st);
 }
 
 __device__ __forceinline__ void kmode_store(char* img, const bf8 (&st)[4]) {
@@ -136,9 +146,9 @@ __device__ __forceinline__ void mnmode_prepare(const ConvGeom& g, int mn0, int M
   }
 }
 
-template <int MODE>
-__device__ __forceinline__ void mnmode_load(const bf16_t* __restrict__ X, long long ld, const ConvGeom& g, int mn0,
-                                            int k0, int K, const ColCtx& cc, bf8 (&st)[4]) {
+template <int MODE, bool WRAP>
+__device__ __forceinline__ void mnmode_load_form(const bf16_t* __restrict__ X, long long ld, const ConvGeom& g, int mn0,
+                                                 int k0, int K, const ColCtx& cc, bf8 (&st)[4]) {
   const int tid = threadIdx.x;
   const int col = mn0 + 8 * (tid & 15);
 #pragma unroll
@@ -152,13 +162,21 @@ __device__ __forceinline__ void mnmode_load(const bf16_t* __restrict__ X, long l
       const int hw = g.RH * g.RW;
       const int n = kk / hw, rem = kk - n * hw;
       const int p = rem / g.RW, q = rem - p * g.RW;
-      const int y = p * g.stride - g.pad + cc.r, x = q * g.stride - g.pad + cc.s;
+      int y = p * g.stride - g.pad + cc.r, x = q * g.stride - g.pad + cc.s;
+      if (WRAP) { const int u = g.upsample ? 2 : 1; y = wrap_tap(y, u * g.SH, g.pad); x = wrap_tap(x, u * g.SW, g.pad); }
       int sy, sx;
       if (g.upsample) { ok = ok && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
       else { ok = ok && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
       st[i] = ok ? ld8(X + ((long long)(n * g.SH + sy) * g.SW + sx) * g.ld + cc.ch) : zero8();
     }
   }
+}
+
+template <int MODE>
+__device__ __forceinline__ void mnmode_load(const bf16_t* __restrict__ X, long long ld, const ConvGeom& g, int mn0,
+                                            int k0, int K, const ColCtx& cc, bf8 (&st)[4]) {
+  if (MODE == OPM_CONV_WGRAD && g.circular) mnmode_load_form<MODE, true>(X, ld, g, mn0, k0, K, cc, st);
+  else mnmode_load_form<MODE, false>(X, ld, g, mn0, k0, K, cc, st);
 }
 
 __device__ __forceinline__ void mnmode_store(char* img, const bf8 (&st)[4]) {

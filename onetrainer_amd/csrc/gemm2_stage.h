@@ -32,7 +32,10 @@ struct ConvGeom {
   int RH, RW;        // spatial dims decoding a GEMM row index (fwd: output, dgrad: input, wgrad: output)
   int KH, KW, stride, pad;
   int upsample;      // source read through a virtual nearest-2x upsample (fwd / wgrad)
-  int pad_;
+  union {
+    int circular;    // circular padding: a tap in the padding margin reads the opposite edge of its image (wrap_tap)
+    int pad_;        // the field's reserved name; 0 = zero padding
+  };
   long long ld;      // pixel stride of the source, elements
 };
 
@@ -83,6 +86,29 @@ OTAMD_HD Mixed3 mixed2_add(const Mixed3& a, const Mixed3& d, int e, int r0) {
 // (m d - 2^32 < d, so the error term x (m d - 2^32) / (2^32 d) stays below 1 / d); coordinates here are far below 2^16
 OTAMD_HD unsigned recip_magic(int d) { return d >= 2 ? 0xFFFFFFFFu / (unsigned)d + 1u : 0u; }
 OTAMD_HD int div_magic(int x, unsigned m) { return (int)(((unsigned long long)(unsigned)x * m) >> 32); }
+
+// Circular padding.  H: the size of the grid the taps address (2 SH under upsample).  Forward / weight-gradient tap
+// coordinate y = p stride + r - pad: the margin [-pad, 0) reads y + H, the margin [H, H + pad) reads y - H, anything
+// further out (only through an output larger than the computed one, pad = 0) stays outside and is zero-filled.  One
+// compare and one add of a launch-uniform value per margin; pad <= H, so one step is enough.  A row past M has
+// y = -NEVER: it stays negative after the add and fails the bound check as before.
+// the margin that wraps: pad under circular padding, else 0 (launch-uniform; the one value the K loop branches on)
+OTAMD_HD int wrap_pad(const ConvGeom& g) { return OTAMD_UNIFORM(g.circular ? g.pad : 0); }
+OTAMD_HD int wrap_tap(int y, int H, int pad) {
+  y += y < 0 ? H : 0;
+  y -= (unsigned)(y - H) < (unsigned)pad ? H : 0;
+  return y;
+}
+// Input gradient: dx[h] takes tap r from the output row p with wrap(p stride + r - pad) = h, so p stride is one of
+// t, t - H, t + H with t = h + pad - r in (-K, H + pad).  An output of the computed size has (P - 1) stride <= H + 2 pad
+// - K <= H - 1 when 2 pad <= K - 1 (the launcher's precondition): the three candidates lie H apart and at most one
+// falls in [0, (P - 1) stride].  That one is t + H where t < 0, t - H where t >= H, else t; its forward coordinate is
+// inside [-pad, H + pad) because every coordinate of such an output is.  With pad = 0 nothing wraps.
+OTAMD_HD int wrap_grad(int t, int H) {
+  t += t < 0 ? H : 0;
+  t -= t >= H ? H : 0;
+  return t;
+}
 
 // Per-lane DMA state of one operand tile (BMN rows/cols x 64 k): BMN/8 pieces of 1 KiB, NW waves
 // take NI = BMN/(8 NW) each (piece j = wave + NW i).
@@ -216,8 +242,16 @@ struct StageIndex {
 
   // source byte offsets of this wave's pieces of the K tile at k0 (OFF_INVALID: zero-fill), incremental form; moves
   // the state on to k0 + 64
+  // One launch-uniform branch per K tile picks the form: the zero-padding form (WRAP = false) is the code without
+  // circular padding, instruction for instruction, so its lanes do no work for the wrap.
   OTAMD_HD void offsets_step(const ConvGeom& g, long long ld, int k0, int Kend, unsigned (&out)[NI]) {
     static_assert(CONV, "plain K / MN operands have no state: offsets()");
+    const int wp = MODE == OPM_CONV_WT ? 0 : wrap_pad(g);
+    if (wp) step_form<true>(g, ld, k0, Kend, wp, out);
+    else step_form<false>(g, ld, k0, Kend, 0, out);
+  }
+  template <bool WRAP>
+  OTAMD_HD void step_form(const ConvGeom& g, long long ld, int k0, int Kend, int wp, unsigned (&out)[NI]) {
     if constexpr (KM) {
       const bool kok = k0 + 8 * (cur.hi & 7) < Kend;
       const int r_ = cur.hi >> 3, s_ = cur.mid, ch = cur.lo;
@@ -227,11 +261,17 @@ struct StageIndex {
         bool v = kok;   // a row past M has y = -NEVER
         int sy, sx;
         if constexpr (MODE == OPM_CONV_FWD) {
-          const int y = b[i] + r_, x = c[i] + s_;
-          if (g.upsample) { v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
-          else { v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
+          int y = b[i] + r_, x = c[i] + s_;
+          if (g.upsample) {
+            if constexpr (WRAP) { y = wrap_tap(y, 2 * g.SH, wp); x = wrap_tap(x, 2 * g.SW, wp); }
+            v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1;
+          } else {
+            if constexpr (WRAP) { y = wrap_tap(y, g.SH, wp); x = wrap_tap(x, g.SW, wp); }
+            v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x;
+          }
         } else {
-          const int ty = b[i] - r_, tx = c[i] - s_;
+          int ty = b[i] - r_, tx = c[i] - s_;
+          if constexpr (WRAP) { ty = wrap_grad(ty, g.RH); tx = wrap_grad(tx, g.RW); }   // before the division
           if (g.stride == 1) { sy = ty; sx = tx; }
           else {   // ty, tx >= 0 where valid: the quotient by the stride's reciprocal, exact when it multiplies back
             sy = div_magic(ty, smagic); sx = div_magic(tx, smagic);
@@ -261,10 +301,15 @@ struct StageIndex {
         bool v = k0 + wg_krow(i) < Kend;
         const int bt = b[ci(i)];
         const Mixed3 px = i == 0 ? cur : mixed3_add(cur, du[i], ROWS_EVEN ? 0 : (a[i] & 127) - (a[0] & 127) - UROWS(i), g.RH, g.RW);
-        const int y = px.mid * g.stride + (bt >> 16), x = px.lo * g.stride + (int)(short)(bt & 0xffff);
+        int y = px.mid * g.stride + (bt >> 16), x = px.lo * g.stride + (int)(short)(bt & 0xffff);
         int sy, sx;
-        if (g.upsample) { v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
-        else { v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
+        if (g.upsample) {
+          if constexpr (WRAP) { y = wrap_tap(y, 2 * g.SH, wp); x = wrap_tap(x, 2 * g.SW, wp); }
+          v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1;
+        } else {
+          if constexpr (WRAP) { y = wrap_tap(y, g.SH, wp); x = wrap_tap(x, g.SW, wp); }
+          v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x;
+        }
         if (v) off = src_off(g, px.hi, sy, sx, wg_ch(i));
         out[i] = off;
       }
@@ -275,6 +320,12 @@ struct StageIndex {
   // source byte offsets of this wave's pieces of the K tile at k0 (OFF_INVALID: zero-fill), closed form: the plain
   // K / MN operands, and the reference of the conv gathers (before start(): it reads the tap index in b[])
   OTAMD_HD void offsets(const ConvGeom& g, long long ld, int k0, int Kend, unsigned (&out)[NI]) const {
+    const int wp = (CONV && MODE != OPM_CONV_WT) ? wrap_pad(g) : 0;
+    if (wp) closed_form<true>(g, ld, k0, Kend, wp, out);
+    else closed_form<false>(g, ld, k0, Kend, 0, out);
+  }
+  template <bool WRAP>
+  OTAMD_HD void closed_form(const ConvGeom& g, long long ld, int k0, int Kend, int wp, unsigned (&out)[NI]) const {
     if constexpr (KM) {
       const int k = k0 + 8 * t0;
       const bool kok = k < Kend;
@@ -294,11 +345,17 @@ struct StageIndex {
           bool v = kok && ok[i];
           int sy, sx;
           if constexpr (MODE == OPM_CONV_FWD) {
-            const int y = b[i] + r_, x = c[i] + s_;
-            if (g.upsample) { v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
-            else { v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
+            int y = b[i] + r_, x = c[i] + s_;
+            if (g.upsample) {
+              if constexpr (WRAP) { y = wrap_tap(y, 2 * g.SH, wp); x = wrap_tap(x, 2 * g.SW, wp); }
+              v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1;
+            } else {
+              if constexpr (WRAP) { y = wrap_tap(y, g.SH, wp); x = wrap_tap(x, g.SW, wp); }
+              v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x;
+            }
           } else {
-            const int ty = b[i] - r_, tx = c[i] - s_;
+            int ty = b[i] - r_, tx = c[i] - s_;
+            if constexpr (WRAP) { ty = wrap_grad(ty, g.RH); tx = wrap_grad(tx, g.RW); }   // before the division
             if (g.stride == 1) { sy = ty; sx = tx; }
             else {
               v = v && ty >= 0 && tx >= 0 && (ty % g.stride) == 0 && (tx % g.stride) == 0;
@@ -329,10 +386,15 @@ struct StageIndex {
           const int n = kk / hw, rem = kk - n * hw;
           const int p = rem / g.RW, q = rem - p * g.RW;
           const int tr = b[i] / g.KW, ts = b[i] - (b[i] / g.KW) * g.KW;
-          const int y = p * g.stride - g.pad + tr, x = q * g.stride - g.pad + ts;
+          int y = p * g.stride - g.pad + tr, x = q * g.stride - g.pad + ts;
           int sy, sx;
-          if (g.upsample) { v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1; }
-          else { v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x; }
+          if (g.upsample) {
+            if constexpr (WRAP) { y = wrap_tap(y, 2 * g.SH, wp); x = wrap_tap(x, 2 * g.SW, wp); }
+            v = v && y >= 0 && y < 2 * g.SH && x >= 0 && x < 2 * g.SW; sy = y >> 1; sx = x >> 1;
+          } else {
+            if constexpr (WRAP) { y = wrap_tap(y, g.SH, wp); x = wrap_tap(x, g.SW, wp); }
+            v = v && y >= 0 && y < g.SH && x >= 0 && x < g.SW; sy = y; sx = x;
+          }
           if (v) off = (unsigned)(((n * g.SH + sy) * g.SW + sx) * (int)g.ld + c[i]) * 2u;
         }
         out[i] = off;

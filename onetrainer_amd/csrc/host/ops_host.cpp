@@ -331,12 +331,21 @@ Tensor linear_wgrad(const Tensor& dy, const Tensor& x, const optional<Tensor>& o
 
 // ---- convolutions: NHWC activations, weights [Cout][KH][KW][Cin] ----
 ConvGeom geom(int64_t N, int64_t SH, int64_t SW, int64_t SC, int64_t RH, int64_t RW, int64_t KH, int64_t KW,
-              int64_t stride, int64_t pad, bool upsample, int64_t ld) {
+              int64_t stride, int64_t pad, bool upsample, int64_t ld, bool circular = false) {
   ConvGeom g;
   std::memset(&g, 0, sizeof(g));
+  g.circular = circular;
   g.N = (int)N; g.SH = (int)SH; g.SW = (int)SW; g.SC = (int)SC; g.RH = (int)RH; g.RW = (int)RW;
   g.KH = (int)KH; g.KW = (int)KW; g.stride = (int)stride; g.pad = (int)pad; g.upsample = upsample; g.ld = ld;
   return g;
+}
+
+// circular padding on the H x W grid the taps address (2H x 2W under upsample): kernels.py's _circular_checks
+void circular_checks(bool circular, int64_t H, int64_t W, int64_t k, int64_t pad, bool up) {
+  if (!circular) return;
+  const int64_t f = up ? 2 : 1;
+  req(0 <= pad && pad <= f * H && pad <= f * W, "circular padding: pad must not exceed the image size");
+  req(2 * pad <= k - 1, "circular padding: 2 * pad <= k - 1");
 }
 
 std::pair<int64_t, int64_t> conv_out_hw(int64_t H, int64_t W, int64_t k, int64_t stride, int64_t pad, bool up) {
@@ -357,10 +366,11 @@ Nhwc nhwc(const Tensor& x) {
 Tensor conv2d(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, int64_t stride, int64_t pad,
               bool upsample, const optional<Tensor>& residual, const optional<Tensor>& rowvec,
               const optional<Tensor>& out, const optional<Tensor>& lora_t, const optional<Tensor>& lora_b2,
-              int64_t out_h, int64_t out_w, int64_t stream) {
+              int64_t out_h, int64_t out_w, int64_t stream, bool circular) {
   const Nhwc s = nhwc(x);
   req(w.dim() == 4, "conv weight [Cout,KH,KW,Cin]");
   const int64_t Cout = w.size(0), KH = w.size(1), KW = w.size(2);
+  circular_checks(circular, s.H, s.W, KH, pad, upsample);
   req(w.size(3) == s.C && is_bf16(w) && w.is_contiguous() && Cout % 8 == 0, "conv weight [Cout,KH,KW,Cin]");
   req(aligned(x) && aligned(w), "aligned operands");
   auto pq = conv_out_hw(s.H, s.W, KH, stride, pad, upsample);
@@ -376,7 +386,7 @@ Tensor conv2d(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, in
       "conv out");
   GemmArgs a = new_args();
   a.A = x.data_ptr(); a.lda = 8; a.amode = OPM_CONV_FWD;
-  a.ga = geom(s.N, s.H, s.W, s.C, Pp, Q, KH, KW, stride, pad, upsample, s.ld);
+  a.ga = geom(s.N, s.H, s.W, s.C, Pp, Q, KH, KW, stride, pad, upsample, s.ld, circular);
   a.B = w.data_ptr(); a.ldb = KH * KW * s.C; a.bmode = OPM_K;
   a.C = o.data_ptr(); a.ldc = Cout;
   a.M = (int)M; a.N = (int)Cout; a.K = (int)(KH * KW * s.C);
@@ -394,10 +404,11 @@ Tensor conv2d(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, in
 // conv forward + LoRA with the down-projection (the base 3x3 geometry, in -> r) fused; t_out [N, P, Q, r]
 Tensor conv2d_lora(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, int64_t stride, int64_t pad,
                    bool upsample, const optional<Tensor>& residual, const optional<Tensor>& rowvec, const Tensor& down,
-                   const Tensor& up2, const Tensor& t_out, int64_t r, int64_t stream) {
+                   const Tensor& up2, const Tensor& t_out, int64_t r, int64_t stream, bool circular) {
   const Nhwc s = nhwc(x);
   req(w.dim() == 4 && down.dim() == 4, "conv weight [Cout,KH,KW,Cin]");
   const int64_t Cout = w.size(0), KH = w.size(1), KW = w.size(2);
+  circular_checks(circular, s.H, s.W, KH, pad, upsample);
   req(w.size(3) == s.C && is_bf16(w) && w.is_contiguous() && Cout % 8 == 0 && aligned(x) && aligned(w), "conv weight");
   req(down.size(1) == KH && down.size(2) == KW && down.size(3) == s.C && down.is_contiguous() && up2.dim() == 2 &&
       up2.size(0) == Cout && up2.size(1) == down.size(0), "conv2d_lora: LoRA shapes");
@@ -407,7 +418,7 @@ Tensor conv2d_lora(const Tensor& x, const Tensor& w, const optional<Tensor>& bia
   Tensor o = at::empty({s.N, Pp, Q, Cout}, x.options());
   GemmArgs a = new_args();
   a.A = x.data_ptr(); a.lda = 8; a.amode = OPM_CONV_FWD;
-  a.ga = geom(s.N, s.H, s.W, s.C, Pp, Q, KH, KW, stride, pad, upsample, s.ld);
+  a.ga = geom(s.N, s.H, s.W, s.C, Pp, Q, KH, KW, stride, pad, upsample, s.ld, circular);
   a.B = w.data_ptr(); a.ldb = Kc; a.bmode = OPM_K;
   a.C = o.data_ptr(); a.ldc = Cout;
   a.M = (int)M; a.N = (int)Cout; a.K = (int)Kc;
@@ -420,21 +431,22 @@ Tensor conv2d_lora(const Tensor& x, const Tensor& w, const optional<Tensor>& bia
     return o;
   }
   ++g_lora_split;
-  conv2d(x, down, {}, stride, pad, upsample, {}, {}, t_out, {}, {}, 0, 0, stream);
-  return conv2d(x, w, bias, stride, pad, upsample, residual, rowvec, o, t_out, up2, 0, 0, stream);
+  conv2d(x, down, {}, stride, pad, upsample, {}, {}, t_out, {}, {}, 0, 0, stream, circular);
+  return conv2d(x, w, bias, stride, pad, upsample, residual, rowvec, o, t_out, up2, 0, 0, stream, circular);
 }
 
 Tensor conv2d_dgrad(const Tensor& dy, const Tensor& w, int64_t H, int64_t W, int64_t stride, int64_t pad,
-                    const optional<Tensor>& out, bool accumulate, int64_t stream) {
+                    const optional<Tensor>& out, bool accumulate, int64_t stream, bool circular) {
   const Nhwc s = nhwc(dy);
   req(w.dim() == 4, "w [Cout,KH,KW,Cin]");
   const int64_t KH = w.size(1), KW = w.size(2), Cin = w.size(3);
+  circular_checks(circular, H, W, KH, pad, false);
   req(w.size(0) == s.C && w.is_contiguous() && Cin % 8 == 0 && s.C % 8 == 0 && aligned(w), "w [Cout,KH,KW,Cin]");
   req(conv_out_hw(H, W, KH, stride, pad, false) == std::make_pair(s.H, s.W), "dgrad geometry");
   Tensor o = out ? *out : at::empty({s.N, H, W, Cin}, dy.options());
   GemmArgs a = new_args();
   a.A = dy.data_ptr(); a.lda = 8; a.amode = OPM_CONV_DGRAD;
-  a.ga = geom(s.N, s.H, s.W, s.C, H, W, KH, KW, stride, pad, false, s.ld);
+  a.ga = geom(s.N, s.H, s.W, s.C, H, W, KH, KW, stride, pad, false, s.ld, circular);
   a.B = w.data_ptr(); a.ldb = Cin; a.bmode = kOpmConvWT;
   a.gb = geom(s.N, s.H, s.W, s.C, H, W, KH, KW, stride, pad, false, Cin);
   a.C = o.data_ptr(); a.ldc = Cin; a.accumulate = accumulate;
@@ -445,8 +457,9 @@ Tensor conv2d_dgrad(const Tensor& dy, const Tensor& w, int64_t H, int64_t W, int
 
 Tensor conv2d_wgrad(const Tensor& dy, const Tensor& x, int64_t ksize, int64_t stride, int64_t pad, bool upsample,
                     const optional<Tensor>& out, bool accumulate, int64_t splits, const optional<Tensor>& bias_grad,
-                    bool bias_acc, int64_t stream) {
+                    bool bias_acc, int64_t stream, bool circular) {
   const Nhwc d = nhwc(dy), s = nhwc(x);
+  circular_checks(circular, s.H, s.W, ksize, pad, upsample);
   req(d.N == s.N && conv_out_hw(s.H, s.W, ksize, stride, pad, upsample) == std::make_pair(d.H, d.W), "wgrad geometry");
   Tensor o = out ? *out : at::empty({d.C, ksize, ksize, s.C}, dy.options());
   req(o.dim() == 4 && o.size(0) == d.C && o.size(1) == ksize && o.size(2) == ksize && o.size(3) == s.C &&
@@ -454,7 +467,7 @@ Tensor conv2d_wgrad(const Tensor& dy, const Tensor& x, int64_t ksize, int64_t st
   GemmArgs a = new_args();
   a.A = dy.data_ptr(); a.lda = d.ld; a.amode = OPM_MN;
   a.B = x.data_ptr(); a.ldb = 8; a.bmode = OPM_CONV_WGRAD;
-  a.gb = geom(s.N, s.H, s.W, s.C, d.H, d.W, ksize, ksize, stride, pad, upsample, s.ld);
+  a.gb = geom(s.N, s.H, s.W, s.C, d.H, d.W, ksize, ksize, stride, pad, upsample, s.ld, circular);
   a.C = o.data_ptr(); a.ldc = ksize * ksize * s.C; a.c_f32 = is_f32(o); a.accumulate = accumulate;
   a.M = (int)d.C; a.N = (int)(ksize * ksize * s.C); a.K = (int)(d.N * d.H * d.W);
   bias_grad_args(a, bias_grad, bias_acc, d.C);
@@ -674,17 +687,18 @@ PYBIND11_MODULE(_otamd_host, m) {
   m.def("linear", &linear);
   m.def("linear_dgrad", &linear_dgrad);
   m.def("linear_wgrad", &linear_wgrad);
-  m.def("conv2d", &conv2d);
+  // circular: a trailing, defaulted argument (earlier positional callers stay valid)
+  m.def("conv2d", &conv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("stride"), py::arg("pad"), py::arg("upsample"), py::arg("residual"), py::arg("rowvec"), py::arg("out"), py::arg("lora_t"), py::arg("lora_b2"), py::arg("out_h"), py::arg("out_w"), py::arg("stream"), py::arg("circular") = false);
   m.def("linear_lora", &linear_lora);
   m.def("linear_dgrad_lora", &linear_dgrad_lora);
   m.def("lora_plan", &otamd_lora_plan);   // the library's lookup as this module links it (tests)
   m.def("lora_dgrad_fused_counts",
         []() { return std::make_pair((long long)g_lora_dgrad_fused, (long long)g_lora_dgrad_split); });
-  m.def("conv2d_lora", &conv2d_lora);
+  m.def("conv2d_lora", &conv2d_lora, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("stride"), py::arg("pad"), py::arg("upsample"), py::arg("residual"), py::arg("rowvec"), py::arg("down"), py::arg("up2"), py::arg("t_out"), py::arg("r"), py::arg("stream"), py::arg("circular") = false);
   m.def("set_lora_fuse", &set_lora_fuse);
   m.def("lora_fused_counts", []() { return std::make_pair((long long)g_lora_fused, (long long)g_lora_split); });
-  m.def("conv2d_dgrad", &conv2d_dgrad);
-  m.def("conv2d_wgrad", &conv2d_wgrad);
+  m.def("conv2d_dgrad", &conv2d_dgrad, py::arg("dy"), py::arg("w"), py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("pad"), py::arg("out"), py::arg("accumulate"), py::arg("stream"), py::arg("circular") = false);
+  m.def("conv2d_wgrad", &conv2d_wgrad, py::arg("dy"), py::arg("x"), py::arg("ksize"), py::arg("stride"), py::arg("pad"), py::arg("upsample"), py::arg("out"), py::arg("accumulate"), py::arg("splits"), py::arg("bias_grad"), py::arg("bias_acc"), py::arg("stream"), py::arg("circular") = false);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd_res", &layernorm_bwd_res);
   m.def("layernorm_param_grad", &layernorm_param_grad);

@@ -63,6 +63,7 @@ def attach_cache_encoders(model, config, device) -> None:
     fam = _family(cfg.model_type)
     vcfg = {"sdxl": V.sdxl_vae_config, "sd15": V.sd15_vae_config, "flux": V.flux_vae_config}[fam]
     model.vae_encoder = V.AutoencoderKLEncoder(vcfg(), device, seed=0)
+    model.vae_encoder.circular = bool(getattr(cfg, "force_circular_padding", False))   # as the model setup sets it
     model.text_encoder_1 = TE.CLIPTextEncoder(TE.clip_l_config(), device)
     if fam == "sdxl":
         model.text_encoder_2 = TE.CLIPTextEncoder(TE.clip_bigg_config(), device)

@@ -571,13 +571,14 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, bias, residual, down: torch.Te
 
 
 def conv2d_lora(x: torch.Tensor, w: torch.Tensor, bias, stride, pad, upsample, residual, rowvec, down: torch.Tensor,
-                up2: torch.Tensor, t_out: torch.Tensor, rank: int, tile=None) -> torch.Tensor:
+                up2: torch.Tensor, t_out: torch.Tensor, rank: int, tile=None, circular=False) -> torch.Tensor:
     """conv2d + LoRA (LoRAModule.py:142-155 conv branch: down = the base geometry in -> r, up = 1x1 r -> out) with the
     down-projection fused into the base conv GEMM when the plan allows; t_out [N, P, Q, r]."""
+    _circular_checks(circular, x.shape[1], x.shape[2], w.shape[1], pad, upsample)
     h = _host()
     if h is not None and tile is None:
         return h.conv2d_lora(x, w, bias, stride, pad, upsample, residual, rowvec, down, up2, t_out, rank,
-                             stream_handle())
+                             stream_handle(), bool(circular))
     N, H, W, Cin, ldx = _nhwc(x)
     Cout, KH, KW, Cin2 = w.shape
     _req(Cin2 == Cin and w.dtype == BF16 and w.is_contiguous() and Cout % 8 == 0 and _aligned(x) and _aligned(w),
@@ -589,7 +590,7 @@ def conv2d_lora(x: torch.Tensor, w: torch.Tensor, bias, stride, pad, upsample, r
     out = torch.empty((N, P, Q, Cout), dtype=BF16, device=x.device)
     a = _new_args()
     a.A, a.lda, a.amode = _p(x), 8, OPM_CONV_FWD
-    a.ga = _geom(N, H, W, Cin, P, Q, KH, KW, stride, pad, upsample, ldx)
+    a.ga = _geom(N, H, W, Cin, P, Q, KH, KW, stride, pad, upsample, ldx, circular)
     a.B, a.ldb, a.bmode = _p(w), Kc, OPM_K
     a.C, a.ldc = _p(out), Cout
     a.M, a.N, a.K = M, Cout, Kc
@@ -598,9 +599,9 @@ def conv2d_lora(x: torch.Tensor, w: torch.Tensor, bias, stride, pad, upsample, r
     if _lora_down_fused(a, down.view(down.shape[0], Kc), up2, t_out.view(M, down.shape[0]), Kc, rank, Cout, x.device,
                         tile=tile):
         return out
-    conv2d(x, down, stride=stride, pad=pad, upsample=upsample, out=t_out)
+    conv2d(x, down, stride=stride, pad=pad, upsample=upsample, out=t_out, circular=circular)
     return conv2d(x, w, bias=bias, stride=stride, pad=pad, upsample=upsample, residual=residual, rowvec=rowvec, out=out,
-                  lora=(t_out, up2))
+                  lora=(t_out, up2), circular=circular)
 
 
 def lora_fused_counts() -> tuple:
@@ -798,11 +799,21 @@ def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, out=None, accumulate=False, 
 
 # ------------------------------------------------------------------------------------------
 # convolutions, NHWC activations, weights [Cout][KH][KW][Cin]
-def _geom(N, SH, SW, SC, RH, RW, KH, KW, stride, pad, upsample, ld) -> ConvGeom:
+def _geom(N, SH, SW, SC, RH, RW, KH, KW, stride, pad, upsample, ld, circular=False) -> ConvGeom:
     g = ConvGeom()
     g.N, g.SH, g.SW, g.SC, g.RH, g.RW = N, SH, SW, SC, RH, RW
     g.KH, g.KW, g.stride, g.pad, g.upsample, g.ld = KH, KW, stride, pad, int(upsample), ld
+    g.circular = int(circular)
     return g
+
+
+def _circular_checks(circular, H, W, k, pad, upsample=False):
+    """the preconditions of circular padding on the H x W grid the taps address (2H x 2W under upsample): torch's own
+    pad <= size, and 2 pad <= k - 1, which leaves the input gradient at most one source per (pixel, tap)."""
+    if circular:
+        f = 2 if upsample else 1
+        _req(0 <= pad <= f * H and pad <= f * W, "circular padding: pad must not exceed the image size")
+        _req(2 * pad <= k - 1, "circular padding: 2 * pad <= k - 1")
 
 
 def conv_out_hw(H, W, k, stride, pad, upsample=False):
@@ -821,16 +832,19 @@ def _nhwc(x: torch.Tensor):
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias=None, stride=1, pad=1, upsample=False, residual=None,
-           rowvec=None, out=None, lora=None, out_hw=None) -> torch.Tensor:
+           rowvec=None, out=None, lora=None, out_hw=None, circular=False) -> torch.Tensor:
     """NHWC conv: y[n,p,q,co] = sum w[co,r,s,ci] * x[n, p*st+r-pad, q*st+s-pad, ci] (+bias, +rowvec[n], +residual).
     upsample=True reads x through a nearest-2x upsample (diffusers Upsample2D).  out_hw overrides the
     output size: taps past the bottom / right edge read zeros, so pad=0 with out_hw = (H/2, W/2)
-    is the VAE Downsample2D's F.pad(x, (0, 1, 0, 1)) + stride-2 conv."""
+    is the VAE Downsample2D's F.pad(x, (0, 1, 0, 1)) + stride-2 conv.  circular=True: a tap inside the padding
+    margin reads the opposite edge of the same image (padding_mode='circular'); out_hw's zeros stay zeros."""
+    _circular_checks(circular, x.shape[1], x.shape[2], w.shape[1], pad, upsample)
     h = _host()
     if h is not None:
         lt, lb = lora if lora is not None else (None, None)
         oh, ow = out_hw if out_hw is not None else (0, 0)
-        return h.conv2d(x, w, bias, stride, pad, upsample, residual, rowvec, out, lt, lb, oh, ow, stream_handle())
+        return h.conv2d(x, w, bias, stride, pad, upsample, residual, rowvec, out, lt, lb, oh, ow, stream_handle(),
+                        bool(circular))
     N, H, W, Cin, ldx = _nhwc(x)
     Cout, KH, KW, Cin2 = w.shape
     _req(Cin2 == Cin and w.dtype == BF16 and w.is_contiguous() and Cout % 8 == 0, "conv weight [Cout,KH,KW,Cin]")
@@ -845,7 +859,7 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias=None, stride=1, pad=1, upsampl
     _req(out.shape == (N, P, Q, Cout) and out.is_contiguous(), "conv out")
     a = _new_args()
     a.A, a.lda, a.amode = _p(x), 8, OPM_CONV_FWD
-    a.ga = _geom(N, H, W, Cin, P, Q, KH, KW, stride, pad, upsample, ldx)
+    a.ga = _geom(N, H, W, Cin, P, Q, KH, KW, stride, pad, upsample, ldx, circular)
     a.B, a.ldb, a.bmode = _p(w), KH * KW * Cin, OPM_K
     a.C, a.ldc = _p(out), Cout
     a.M, a.N, a.K = M, Cout, KH * KW * Cin
@@ -860,12 +874,15 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias=None, stride=1, pad=1, upsampl
 
 
 def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, stride=1, pad=1, out=None,
-                 accumulate=False) -> torch.Tensor:
+                 accumulate=False, circular=False) -> torch.Tensor:
     """dx of conv2d (no upsample): dx[n,h,w,ci] = sum_{r,s,co} dy[n,(h+pad-r)/st,(w+pad-s)/st,co] * w[co,r,s,ci].
-    w is the stored weight [Cout][KH][KW][Cin], read in place (OPM_CONV_WT: no transpose pass)."""
+    w is the stored weight [Cout][KH][KW][Cin], read in place (OPM_CONV_WT: no transpose pass).  circular=True: the
+    exact adjoint of the circular forward (the one wrapped source of each (pixel, tap), csrc/gemm2_stage.h)."""
+    _circular_checks(circular, in_hw[0], in_hw[1], w.shape[1], pad)
     h = _host()
     if h is not None:
-        return h.conv2d_dgrad(dy, w, in_hw[0], in_hw[1], stride, pad, out, accumulate, stream_handle())
+        return h.conv2d_dgrad(dy, w, in_hw[0], in_hw[1], stride, pad, out, accumulate, stream_handle(),
+                              bool(circular))
     N, P, Q, Cout, ldy = _nhwc(dy)
     Cout2, KH, KW, Cin = w.shape
     _req(Cout2 == Cout and w.is_contiguous() and Cin % 8 == 0 and Cout % 8 == 0 and _aligned(w),
@@ -876,7 +893,7 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, stride=1, pad=1, out=
         out = torch.empty((N, H, W, Cin), dtype=BF16, device=dy.device)
     a = _new_args()
     a.A, a.lda, a.amode = _p(dy), 8, OPM_CONV_DGRAD
-    a.ga = _geom(N, P, Q, Cout, H, W, KH, KW, stride, pad, False, ldy)
+    a.ga = _geom(N, P, Q, Cout, H, W, KH, KW, stride, pad, False, ldy, circular)
     a.B, a.ldb, a.bmode = _p(w), Cin, OPM_CONV_WT
     a.gb = _geom(N, P, Q, Cout, H, W, KH, KW, stride, pad, False, Cin)
     a.C, a.ldc, a.accumulate = _p(out), Cin, int(accumulate)
@@ -886,14 +903,15 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, stride=1, pad=1, out=
 
 
 def conv2d_wgrad(dy: torch.Tensor, x: torch.Tensor, ksize=3, stride=1, pad=1, upsample=False, out=None,
-                 accumulate=False, splits=None, bias_grad=None, bias_acc=False) -> torch.Tensor:
+                 accumulate=False, splits=None, bias_grad=None, bias_acc=False, circular=False) -> torch.Tensor:
     """dw[co,r,s,ci] = sum_{n,p,q} dy[n,p,q,co] * x[n, p*st+r-pad, q*st+s-pad, ci]; bias_grad [Cout]: also
-    db = sum_{n,p,q} dy[n,p,q,:] fused into the same GEMM."""
+    db = sum_{n,p,q} dy[n,p,q,:] fused into the same GEMM.  circular=True: x read as the circular forward reads it."""
+    _circular_checks(circular, x.shape[1], x.shape[2], ksize, pad, upsample)
     h = _host()
     if h is not None:
         return h.conv2d_wgrad(dy, x, ksize, stride, pad, upsample, out, accumulate, splits or 0, bias_grad,
                               bias_acc,
-                              stream_handle())
+                              stream_handle(), bool(circular))
     N, P, Q, Cout, ldy = _nhwc(dy)
     N2, H, W, Cin, ldx = _nhwc(x)
     _req(N == N2 and conv_out_hw(H, W, ksize, stride, pad, upsample) == (P, Q), "wgrad geometry")
@@ -903,7 +921,7 @@ def conv2d_wgrad(dy: torch.Tensor, x: torch.Tensor, ksize=3, stride=1, pad=1, up
     a = _new_args()
     a.A, a.lda, a.amode = _p(dy), ldy, OPM_MN
     a.B, a.ldb, a.bmode = _p(x), 8, OPM_CONV_WGRAD
-    a.gb = _geom(N, H, W, Cin, P, Q, ksize, ksize, stride, pad, upsample, ldx)
+    a.gb = _geom(N, H, W, Cin, P, Q, ksize, ksize, stride, pad, upsample, ldx, circular)
     a.C, a.ldc, a.c_f32, a.accumulate = _p(out), ksize * ksize * Cin, int(out.dtype == F32), int(accumulate)
     Kg = N * P * Q
     a.M, a.N, a.K = Cout, ksize * ksize * Cin, Kg

@@ -186,6 +186,16 @@ def nhwc_pair(data: dict, C: int):
     return p.to(torch.bfloat16).contiguous(), t.contiguous()
 
 
+def set_circular_padding(model, config) -> None:
+    """force_circular_padding (BaseStableDiffusionXLSetup.py:48-52, modules/util/conv_util.py): padding_mode 'circular'
+    on every padded conv of the UNet (base and conv-LoRA down projections: they share the UNet's conv call) and of the
+    VAE halves attached to the model.  A FLUX model has only the VAE's (BaseFluxSetup.py:52-56)."""
+    on = bool(getattr(config, "force_circular_padding", False))
+    for net in (getattr(model, "unet", None), getattr(model, "vae_encoder", None), getattr(model, "vae_decoder", None)):
+        if net is not None:
+            net.circular = on
+
+
 class BaseStableDiffusionXLSetup:
     def __init__(self, train_device, temp_device=None, debug_mode=False, dp_rank=0, dp_world=1):
         self.train_device = torch.device(train_device)

@@ -9,6 +9,7 @@ from ..util.NamedParameterGroup import NamedParameterGroup, NamedParameterGroupC
 from ..util.create import create_optimizer
 from ..util.optimizer_util import restore_training_state
 from .BaseFluxSetup import BaseFluxSetup
+from .BaseStableDiffusionXLSetup import set_circular_padding
 from ..util.config.plain import plain
 
 
@@ -27,6 +28,7 @@ class FluxFineTuneSetup(BaseFluxSetup):
         config = plain(config)
         model.dtype_plan = dtype_plan(config)   # util/dtype_util.py: the config's dtypes honoured, overridden or refused
         model.train_dtype = torch.bfloat16
+        set_circular_padding(model, config)
 
     def setup_model(self, model, config):
         config = plain(config)

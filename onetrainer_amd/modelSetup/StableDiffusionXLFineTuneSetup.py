@@ -8,7 +8,7 @@ from ..util.dtype_util import dtype_plan
 from ..util.NamedParameterGroup import NamedParameterGroup, NamedParameterGroupCollection
 from ..util.create import create_optimizer
 from ..util.optimizer_util import restore_training_state
-from .BaseStableDiffusionXLSetup import BaseStableDiffusionXLSetup
+from .BaseStableDiffusionXLSetup import BaseStableDiffusionXLSetup, set_circular_padding
 from ..util.config.plain import plain
 
 
@@ -28,6 +28,7 @@ class StableDiffusionXLFineTuneSetup(BaseStableDiffusionXLSetup):
         config = plain(config)
         model.dtype_plan = dtype_plan(config)   # util/dtype_util.py: the config's dtypes honoured, overridden or refused
         model.train_dtype = torch.bfloat16
+        set_circular_padding(model, config)
 
     def setup_model(self, model, config):
         config = plain(config)

@@ -14,7 +14,7 @@ from ..module.lora import PRESETS, LoRAUNetWrapper
 from ..util.NamedParameterGroup import NamedParameterGroup, NamedParameterGroupCollection
 from ..util.create import create_optimizer
 from ..util.optimizer_util import restore_training_state
-from .BaseStableDiffusionXLSetup import BaseStableDiffusionXLSetup
+from .BaseStableDiffusionXLSetup import BaseStableDiffusionXLSetup, set_circular_padding
 from ..util.config.plain import plain
 
 
@@ -33,6 +33,7 @@ class StableDiffusionXLLoRASetup(BaseStableDiffusionXLSetup):
         config = plain(config)
         model.dtype_plan = dtype_plan(config)   # util/dtype_util.py: the config's dtypes honoured, overridden or refused
         model.train_dtype = torch.bfloat16
+        set_circular_padding(model, config)
 
     @staticmethod
     def layer_filter(config):

@@ -345,14 +345,15 @@ def linear_w8(x, wref: W8Ref, bref=None, residual=None, lora=None):
 
 class ConvFn(torch.autograd.Function):
     """NHWC conv 3x3 (pad 1), stride 1/2, optional virtual nearest-2x upsample of the input,
-    epilogue + bias + rowvec[n] (ResnetBlock2D time-embedding projection) + residual."""
+    epilogue + bias + rowvec[n] (ResnetBlock2D time-embedding projection) + residual.  circular: padding_mode
+    'circular' (force_circular_padding), carried into both gradients."""
 
     @staticmethod
-    def forward(ctx, x, wref, bref, rowvec, residual, stride, upsample, *params):
+    def forward(ctx, x, wref, bref, rowvec, residual, stride, upsample, circular, *params):
         y = K.conv2d(x, wref.w, bias=bref.w if bref is not None else None, stride=stride, pad=1, upsample=upsample,
-                     residual=residual, rowvec=rowvec)
+                     residual=residual, rowvec=rowvec, circular=circular)
         ctx.save_for_backward(x)
-        ctx.wref, ctx.bref, ctx.stride, ctx.upsample = wref, bref, stride, upsample
+        ctx.wref, ctx.bref, ctx.stride, ctx.upsample, ctx.circular = wref, bref, stride, upsample, circular
         ctx.has_rowvec, ctx.has_res = rowvec is not None, residual is not None
         return y
 
@@ -369,16 +370,17 @@ class ConvFn(torch.autograd.Function):
             with S.wgrad_region((dy, x)):
                 if wref.trainable:   # + the bias gradient from the same GEMM's dy images
                     K.conv2d_wgrad(dy, x, 3, ctx.stride, 1, upsample=ctx.upsample, out=wref.g, accumulate=wref.acc(),
-                                   bias_grad=bref.g.view(-1) if btr else None, bias_acc=btr and bref.acc())
+                                   bias_grad=bref.g.view(-1) if btr else None, bias_acc=btr and bref.acc(),
+                                   circular=ctx.circular)
                 elif btr:
                     K.colsum(dy, out=bref.g.view(1, -1), accumulate=bref.acc())
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.upsample:
-                dup = K.conv2d_dgrad(dy, wref.w, (2 * H, 2 * W), 1, 1)
+                dup = K.conv2d_dgrad(dy, wref.w, (2 * H, 2 * W), 1, 1, circular=ctx.circular)
                 dx = K.upsample2x_bwd(dup)
             else:
-                dx = K.conv2d_dgrad(dy, wref.w, (H, W), ctx.stride, 1)
+                dx = K.conv2d_dgrad(dy, wref.w, (H, W), ctx.stride, 1, circular=ctx.circular)
         drow = None
         P, Q = dy.shape[1], dy.shape[2]
         if ctx.has_rowvec:
@@ -389,7 +391,7 @@ class ConvFn(torch.autograd.Function):
         if btr:
             bref.done()
         dres = dy if ctx.has_res else None
-        return (dx, None, None, drow, dres, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
+        return (dx, None, None, drow, dres, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 8)
 
 
 class LoraConvFn(torch.autograd.Function):
@@ -397,20 +399,21 @@ class LoraConvFn(torch.autograd.Function):
     up = 1x1 r->out fused into the base conv GEMM as its second K segment; frozen base."""
 
     @staticmethod
-    def forward(ctx, x, wref, bref, rowvec, residual, stride, upsample, site, *params):
+    def forward(ctx, x, wref, bref, rowvec, residual, stride, upsample, circular, site, *params):
         Ho, Wo = K.conv_out_hw(x.shape[1], x.shape[2], site.k, stride, 1, upsample)
         t = torch.empty((x.shape[0], Ho, Wo, site.down.shape[0]), dtype=x.dtype, device=x.device)
         drop = site.drop()
         if drop is not None:   # LoRA dropout: the two-launch form with the mask on t in between (LoraLinearFn)
-            K.conv2d(x, site.down, stride=stride, pad=1, upsample=upsample, out=t)
+            K.conv2d(x, site.down, stride=stride, pad=1, upsample=upsample, out=t, circular=circular)
             drop.dropout(t, site)
             y = K.conv2d(x, wref.w, bias=bref.w if bref is not None else None, stride=stride, pad=1, upsample=upsample,
-                         residual=residual, rowvec=rowvec, lora=(t, site.up2))
+                         residual=residual, rowvec=rowvec, lora=(t, site.up2), circular=circular)
         else:
             y = K.conv2d_lora(x, wref.w, bref.w if bref is not None else None, stride, 1, upsample, residual, rowvec,
-                              site.down, site.up2, t, site.rank)
+                              site.down, site.up2, t, site.rank, circular=circular)
         ctx.save_for_backward(x, t)
         ctx.wref, ctx.bref, ctx.stride, ctx.upsample, ctx.site = wref, bref, stride, upsample, site
+        ctx.circular = circular
         ctx.has_rowvec, ctx.has_res = rowvec is not None, residual is not None
         return y
 
@@ -433,21 +436,23 @@ class LoraConvFn(torch.autograd.Function):
         btr = bref is not None and bref.trainable
         with S.wgrad_region((dy, x, t, u)):
             acc = site.acc()
-            K.conv2d_wgrad(u, x, site.k, ctx.stride, 1, upsample=ctx.upsample, out=site.g_down, accumulate=acc)
+            K.conv2d_wgrad(u, x, site.k, ctx.stride, 1, upsample=ctx.upsample, out=site.g_down, accumulate=acc,
+                           circular=ctx.circular)
             K.linear_wgrad(dy2, t.reshape(M, r), out=site.g_up[0], accumulate=acc, alpha=site.scale)
             if wref.trainable:
-                K.conv2d_wgrad(dy, x, 3, ctx.stride, 1, upsample=ctx.upsample, out=wref.g, accumulate=wref.acc())
+                K.conv2d_wgrad(dy, x, 3, ctx.stride, 1, upsample=ctx.upsample, out=wref.g, accumulate=wref.acc(),
+                               circular=ctx.circular)
             if btr:
                 K.colsum(dy, out=bref.g.view(1, -1), accumulate=bref.acc())
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.upsample:
-                dup = K.conv2d_dgrad(dy, wref.w, (2 * H, 2 * W), 1, 1)
-                K.conv2d_dgrad(u, site.down, (2 * H, 2 * W), 1, 1, out=dup, accumulate=True)
+                dup = K.conv2d_dgrad(dy, wref.w, (2 * H, 2 * W), 1, 1, circular=ctx.circular)
+                K.conv2d_dgrad(u, site.down, (2 * H, 2 * W), 1, 1, out=dup, accumulate=True, circular=ctx.circular)
                 dx = K.upsample2x_bwd(dup)
             else:
-                dx = K.conv2d_dgrad(dy, wref.w, (H, W), ctx.stride, 1)
-                K.conv2d_dgrad(u, site.down, (H, W), ctx.stride, 1, out=dx, accumulate=True)
+                dx = K.conv2d_dgrad(dy, wref.w, (H, W), ctx.stride, 1, circular=ctx.circular)
+                K.conv2d_dgrad(u, site.down, (H, W), ctx.stride, 1, out=dx, accumulate=True, circular=ctx.circular)
         site.done()
         drow = None
         if ctx.has_rowvec:
@@ -457,14 +462,14 @@ class LoraConvFn(torch.autograd.Function):
         if btr:
             bref.done()
         dres = dy if ctx.has_res else None
-        return (dx, None, None, drow, dres, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 8)
+        return (dx, None, None, drow, dres, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 9)
 
 
-def conv(x, wref, bref=None, rowvec=None, residual=None, stride=1, upsample=False, lora=None):
+def conv(x, wref, bref=None, rowvec=None, residual=None, stride=1, upsample=False, lora=None, circular=False):
     if lora is not None:
-        return LoraConvFn.apply(x, wref, bref, rowvec, residual, stride, upsample, lora, *lora.params,
+        return LoraConvFn.apply(x, wref, bref, rowvec, residual, stride, upsample, circular, lora, *lora.params,
                                 *_trainable_params(wref, bref))
-    return ConvFn.apply(x, wref, bref, rowvec, residual, stride, upsample, *_params(wref, bref))
+    return ConvFn.apply(x, wref, bref, rowvec, residual, stride, upsample, circular, *_params(wref, bref))
 
 
 class GroupNormFn(torch.autograd.Function):

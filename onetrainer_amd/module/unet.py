@@ -249,6 +249,9 @@ class UNet2DConditionModel:
         self._refs: dict = {}
         self.lora = None      # module/lora.py LoRAUNetWrapper when training adapters on a frozen base
         self.dora = None      # module/dora.py DoRAWrapper instead, with lora_decompose: adapted GEMMs read merged weights
+        # force_circular_padding: every 3x3 conv, base and conv-LoRA down projection, wraps at the image edges (the
+        # model setup sets it; the 1x1 convs are held as linears and have no padding)
+        self.circular = False
         if seed is not None:
             self.init_weights(seed)
 
@@ -344,7 +347,7 @@ class UNet2DConditionModel:
 
     def _conv(self, x, p, rowvec=None, residual=None, stride=1, upsample=False):
         return Fn.conv(x, self.R(p + ".weight"), self.R(p + ".bias"), rowvec=rowvec, residual=residual, stride=stride,
-                       upsample=upsample, lora=self._lo(p))
+                       upsample=upsample, lora=self._lo(p), circular=self.circular)
 
     def _gn(self, x, p, silu, eps=None):
         cfg = self.cfg

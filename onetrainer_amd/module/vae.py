@@ -150,6 +150,10 @@ class _VAEBlocks:
     """what the encoder and the decoder share: the frozen flat store's parameter plumbing (a subclass supplies specs,
     store, `_assign` and `state_dict` for its own layout) and the AutoencoderKL blocks on the HIP kernels."""
 
+    # force_circular_padding: every padded (3x3, pad 1) conv wraps at the image edges; the model setup sets it.  The
+    # encoder's stride-2 pad-0 downsamplers keep their explicit zero column and row, as diffusers' F.pad does
+    circular = False
+
     # ----- parameters ---------------------------------------------------------------------------
     def init_weights(self, seed: int):
         g = torch.Generator(device=self.device).manual_seed(seed)
@@ -186,14 +190,15 @@ class _VAEBlocks:
 
     def _resnet(self, x, p):
         h = self._gn(x, p + ".norm1", True)
-        h = K.conv2d(h, self.W(p + ".conv1.weight"), bias=self.W(p + ".conv1.bias"))
+        h = K.conv2d(h, self.W(p + ".conv1.weight"), bias=self.W(p + ".conv1.bias"), circular=self.circular)
         h = self._gn(h, p + ".norm2", True)
         sc = x
         if (p + ".conv_shortcut.weight") in self.store.slots:
             N, H, W_, C = x.shape
             sc = K.linear(x.view(-1, C), self.W(p + ".conv_shortcut.weight"),
                           bias=self.W(p + ".conv_shortcut.bias")).view(N, H, W_, -1)
-        return K.conv2d(h, self.W(p + ".conv2.weight"), bias=self.W(p + ".conv2.bias"), residual=sc)
+        return K.conv2d(h, self.W(p + ".conv2.weight"), bias=self.W(p + ".conv2.bias"), residual=sc,
+                        circular=self.circular)
 
     def _attention(self, x, p):
         N, H, W_, C = x.shape
@@ -253,7 +258,8 @@ class AutoencoderKLEncoder(_VAEBlocks):
         ch = cfg.block_out_channels
         K._req(x.shape[1] % (1 << (len(ch) - 1)) == 0 and x.shape[2] % (1 << (len(ch) - 1)) == 0,
                "image size must be a multiple of the VAE downsampling factor")
-        h = K.conv2d(x, self.W("encoder.conv_in.weight"), bias=self.W("encoder.conv_in.bias"))
+        h = K.conv2d(x, self.W("encoder.conv_in.weight"), bias=self.W("encoder.conv_in.bias"),
+                     circular=self.circular)
         for i, c in enumerate(ch):
             for j in range(cfg.layers_per_block):
                 h = self._resnet(h, f"encoder.down_blocks.{i}.resnets.{j}")
@@ -270,9 +276,11 @@ class AutoencoderKLEncoder(_VAEBlocks):
         if not cfg.use_quant_conv:
             # DiagonalGaussianDistribution(conv_out(h)).mean: only conv_out's first L output channels (the stored
             # weight's first L rows), in the reference's autocast dtype
-            mean = K.conv2d(h, self.W("encoder.conv_out.weight")[:L], bias=self.W("encoder.conv_out.bias")[:L])
+            mean = K.conv2d(h, self.W("encoder.conv_out.weight")[:L], bias=self.W("encoder.conv_out.bias")[:L],
+                            circular=self.circular)
             return mean.float()
-        h = K.conv2d(h, self.W("encoder.conv_out.weight"), bias=self.W("encoder.conv_out.bias"))
+        h = K.conv2d(h, self.W("encoder.conv_out.weight"), bias=self.W("encoder.conv_out.bias"),
+                     circular=self.circular)
         N, H, W_, C2 = h.shape
         # DiagonalGaussianDistribution(quant_conv(h)).mean: only the first L quant_conv rows
         mean = K.linear(h.view(-1, C2), self.W("quant_conv.weight")[:L], bias=self.W("quant_conv.bias")[:L],
@@ -415,7 +423,8 @@ class AutoencoderKLDecoder(_VAEBlocks):
         if cfg.use_quant_conv:
             x = K.linear(x.view(-1, Lp), self.W("post_quant_conv.weight"),
                          bias=self.W("post_quant_conv.bias")).view(B, H, W_, Lp)
-        h = K.conv2d(x, self.W("decoder.conv_in.weight"), bias=self.W("decoder.conv_in.bias"))
+        h = K.conv2d(x, self.W("decoder.conv_in.weight"), bias=self.W("decoder.conv_in.bias"),
+                     circular=self.circular)
         h = self._resnet(h, "decoder.mid_block.resnets.0")
         h = self._attention(h, "decoder.mid_block.attentions.0")
         h = self._resnet(h, "decoder.mid_block.resnets.1")
@@ -424,8 +433,10 @@ class AutoencoderKLDecoder(_VAEBlocks):
                 h = self._resnet(h, f"decoder.up_blocks.{i}.resnets.{j}")
             if i < len(ch) - 1:
                 p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-                h = K.conv2d(h, self.W(p + ".weight"), bias=self.W(p + ".bias"), upsample=True)
+                h = K.conv2d(h, self.W(p + ".weight"), bias=self.W(p + ".bias"), upsample=True,
+                             circular=self.circular)
         h = self._gn(h, "decoder.conv_norm_out", True)
-        return K.conv2d(h, self.W("decoder.conv_out.weight"), bias=self.W("decoder.conv_out.bias"))
+        return K.conv2d(h, self.W("decoder.conv_out.weight"), bias=self.W("decoder.conv_out.bias"),
+                        circular=self.circular)
 
     __call__ = decode

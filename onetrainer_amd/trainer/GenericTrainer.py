@@ -169,6 +169,7 @@ class GenericTrainer(TimedActionMixin):
             vcfg = getattr(m, "vae_config", None) or (V.sd15_vae_config() if create.is_sd15(cfg.model_type)
                                                       else V.sdxl_vae_config())
             m.vae_decoder = V.AutoencoderKLDecoder(vcfg, self.device, seed=0)
+            m.vae_decoder.circular = bool(getattr(cfg, "force_circular_padding", False))   # as the model setup sets it
             names = cfg.model_names()
             if load and (names.base_model or names.vae_model):
                 from ..modelLoader.StableDiffusionModelLoader import load_vae_decoder

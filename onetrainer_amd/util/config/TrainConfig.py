@@ -170,6 +170,9 @@ class TrainConfig:
     validation: bool = False
     validate_after: float = 1
     validate_after_unit: str = "EPOCH"
+    # padding_mode 'circular' on every padded conv of the UNet, the VAE and the conv-LoRA down projections, for
+    # tileable images (modules/util/conv_util.py; BaseStableDiffusionSetup.py:51-55)
+    force_circular_padding: bool = False
     text_encoder_layer_skip: int = 0          # TrainConfig.py:873,883
     text_encoder_2_layer_skip: int = 0
     # concepts (TrainConfig.py:793-794): inline list of ConceptConfig dicts, else the concept file
